@@ -17,7 +17,10 @@ round trip into the curve, as SURVEY.md 8-e asks.
     python bench.py --gpus 8 ...          # starts 8 ranks itself (torch.distributed.run, one process per GPU, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
 
-Prints ONE JSON line on rank 0 (see the driver contract).  Extra objects:
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times --steps steps and prints the headline
+(value, ms_per_step, ...); --dump-outputs DIR also writes the last timed step's outputs (prob, grad_scores, index lists, the overlap matrix
+or a fixed sample of it) as .npy files, the inputs being seeded, so that two builds can be compared output for output.
+--full adds the extra objects:
   roofline            the dominant HBM-bound launch of the timed step: algorithmic bytes / its HIP-event duration INSIDE the step
                       sequence (the library brackets the launch with events on its launch stream, gnms_profile_events), against the
                       8 TB/s HBM peak; `ceiling` = what a plain store (load) stream reaches on this device over the same buffers.
@@ -30,7 +33,7 @@ Prints ONE JSON line on rank 0 (see the driver contract).  Extra objects:
   box_counts          N > 1 only: the other box counts north_star names (256, 1024, 16384 per image) at this world size -- whole-job boxes/s,
                       timed like the headline (barrier + sync on both sides, MAX over ranks); at N = 1 the keys N256 / N1024 / N16384 hold them
   hip_graph_replay    the same step as a replayed HIP graph of the C-ABI calls (no host cost per step), 1 GPU only
-  two_calls, dim3_*, N*, B*_N4096   the other shapes of the path (default line only), each with ms_per_step (eager, host included; the median of
+  two_calls, dim3_*, N*, B*_N4096   the other shapes of the path (1-GPU default shape only), each with ms_per_step (eager, host included; the median of
                       three windows of its `steps`, all three in windows_ms), its own
                       roofline brief and device_ms_per_step: the step's time on the device when the host has run ahead (the same
                       eager calls enqueued behind a spin kernel; small shapes are host-bound and hosts differ by 2x between boxes);
@@ -52,6 +55,8 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8.0 TB/s
 REF_CPU_SURVEY = 459.0      # reference lib/groomed_nms.py + lib/core.py iou, torch CPU, 8 threads, uniform N=4096 (not published)
+DUMP_IOU_SAMPLE = 1 << 23   # --dump-outputs: overlap-matrix entries written at most (32 MiB of float32)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def parse():
@@ -77,12 +82,24 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline: keep processing images of the batch for about this long")
     ap.add_argument("--pmc-summary", default=None,
                     help="JSON written by tools/pmc.sh in the same session ({kernel: HBM bytes per launch}); fills roofline.traffic.  Without it "
-                         "the default run collects the counters itself (two short rocprofv3 --pmc passes of this script) when rocprofv3 is on PATH")
+                         "a --full run collects the counters itself (two short rocprofv3 --pmc passes of this script) when rocprofv3 is on PATH")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip what the default 1-GPU line adds by re-running this script: the PMC passes for roofline.traffic, the `two_calls` "
+                    help="skip what the --full 1-GPU line adds by re-running this script: the PMC passes for roofline.traffic, the `two_calls` "
                          "keys (the reference's unchanged call sites in 2D and 3D), the `dim3_*` keys (3D, N = 4096 and 16384) and the other box counts / batches "
                          "north_star names (N256, N1024, N16384, B1_N4096, B4_N4096), timed in this process")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline (+ PMC passes), spread windows, hip_graph_replay, other_kind, the other shapes, "
+                         "box_counts at N > 1, parity against the CPU oracle and cpu_baseline.  Without it the run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed on rank 0 as DIR/<name>.npy (float32; index "
+                         "outputs as float64): prob, grad_scores and, without --graph, order / valid / invalid / num_valid / num_invalid; the "
+                         "overlap matrix as iou.npy, or as iou_sample.npy (%d entries at sorted flat positions drawn by "
+                         "np.random.default_rng(0).integers) when it holds more" % DUMP_IOU_SAMPLE)
+    args = ap.parse_args()
+    if not args.full:                      # a plain run: the headline only
+        args.no_cpu_baseline = args.no_other_kind = args.no_extras = True
+    return args
 
 
 def launch_ranks_if_needed(args):
@@ -106,7 +123,7 @@ def _sub_bench(extra, timeout=900):
     """this script once more with other flags (a child process on the same GPU, this one idle meanwhile); its JSON line as a dict"""
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-other-kind", "--no-extras"] + list(extra)
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-other-kind", "--no-extras"] + list(extra)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if r.returncode != 0 or not lines:
@@ -147,7 +164,7 @@ def _pmc_traffic(workload_args, B, N):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, counter)
             cmd = [exe, "--pmc", counter, "--kernel-trace", "-d", d, "-o", "pmc", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-other-kind", "--no-extras"] + list(workload_args)
+                   "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-other-kind", "--no-extras"] + list(workload_args)
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd="/tmp")
             files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
             if not files:
@@ -167,6 +184,31 @@ def _pmc_traffic(workload_args, B, N):
         traffic[k] = raw["FETCH_SIZE"].get(k, 0.0) * 1024 * 2 + raw["WRITE_SIZE"].get(k, 0.0) * 1024 * wcal
     return traffic, ("rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes with --kernel-trace only, over `bench.py --steps 5`; KiB counters, "
                      "FETCH_SIZE x2 (gfx950), WRITE_SIZE x %.4f (calibrated on prof_fill_kernel's known byte count in the same pass)" % wcal)
+
+
+def dump_outputs(d, state, graph):
+    """--dump-outputs: the last timed step's outputs as d/<name>.npy (see the option's help)."""
+    import torch
+    if graph:
+        prob, grad, iou = state["graph_out"]()
+        named = {"prob": prob, "grad_scores": grad}
+    else:
+        res, iou, scores = state["out"]
+        named = {"prob": res[0], "grad_scores": scores.grad, "order": res[1], "valid": res[2], "invalid": res[3],
+                 "num_valid": res[4], "num_invalid": res[5]}
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32 if v.is_floating_point() else np.float64) for k, v in named.items() if v is not None}
+    flat = iou.reshape(-1)
+    if flat.numel() <= DUMP_IOU_SAMPLE:
+        arrays["iou"] = iou.cpu().numpy()
+    else:
+        pos = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=DUMP_IOU_SAMPLE))
+        arrays["iou_sample"] = flat[torch.from_numpy(pos).to(flat.device)].cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_MAX_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def main():
@@ -208,6 +250,7 @@ def main():
     n_buf = int(min(max(3, -(-(768 << 20) // max(mat_bytes, 1))), 64))
     iou_bufs = [torch.empty((B, N, N), dtype=torch.float32, device=dev) for _ in range(n_buf)]
     state = {"i": 0}
+    keep_outputs = args.dump_outputs is not None and rank == 0
 
     def next_buf():
         state["i"] = (state["i"] + 1) % n_buf
@@ -222,13 +265,16 @@ def main():
         def step():
             buf = next_buf()
             if args.dim == 2 and not args.two_calls:
-                prob = G.differentiable_nms_with_iou2d_batched(scores, boxes, iou_out=buf)[0]       # gnms_forward_with_iou2d
+                res = G.differentiable_nms_with_iou2d_batched(scores, boxes, iou_out=buf)       # gnms_forward_with_iou2d
             elif args.dim == 3 and not args.two_calls:
-                prob = G.differentiable_nms_with_iou3d_batched(scores, boxes, iou_out=buf)[0]       # gnms_forward_with_iou3d
+                res = G.differentiable_nms_with_iou3d_batched(scores, boxes, iou_out=buf)       # gnms_forward_with_iou3d
             else:
-                prob = G.differentiable_nms_batched(scores, build_overlaps(buf))[0]
+                res = G.differentiable_nms_batched(scores, build_overlaps(buf))
+            prob = res[0]
             scores.grad = None
             torch.autograd.backward(prob, w)          # dL/dprob = w
+            if keep_outputs:
+                state["out"] = (res, buf, scores)
             return prob
         return step, build_overlaps
 
@@ -276,6 +322,7 @@ def main():
         def replay():                                 # one replay = one full step
             gstate["i"] = (gstate["i"] + 1) % len(graphs)
             graphs[gstate["i"]].replay()
+        state["graph_out"] = lambda: (prob_g, grad_g, iou_bufs[gstate["i"]])     # what the last replay wrote
         return replay, (lambda: raw_step(next_buf()))
 
     if args.graph:
@@ -289,6 +336,8 @@ def main():
         step()
     torch.cuda.synchronize()
     dt = gdist.timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, heartbeat)
+    if keep_outputs:
+        dump_outputs(args.dump_outputs, state, args.graph)
     # `spread`: the contract's window above is ONE sample of K steps; four more windows of the same K steps right behind it say how far such
     # a sample moves on this box (1 GPU only; `value` is and stays the first window)
     windows = [dt]
@@ -339,96 +388,98 @@ def main():
     out = None
     if rank == 0:
         one_call = not args.two_calls
-        per_box = 16.0 if args.dim == 2 else 28.0
-        alg_write = B * (4.0 * N * N + per_box * N)       # IoU-2D 4N^2 + 16N, IoU-3D (params) 4N^2 + 28N per image
-        alg_read = B * (4.0 * N * N + 16.0 * N)           # NMS forward given the matrix: 4N^2 + 16N per image
-        if args.sorted_scores:                            # only the columns a leader of the row block can sit in are needed
-            alg_read = B * (sum(64 * min(N, 64 * (kb + 1)) for kb in range((N + 63) // 64)) * 4.0 + 16.0 * N)
+        r_write = r_read = None
+        if args.full:
+            per_box = 16.0 if args.dim == 2 else 28.0
+            alg_write = B * (4.0 * N * N + per_box * N)       # IoU-2D 4N^2 + 16N, IoU-3D (params) 4N^2 + 28N per image
+            alg_read = B * (4.0 * N * N + 16.0 * N)           # NMS forward given the matrix: 4N^2 + 16N per image
+            if args.sorted_scores:                            # only the columns a leader of the row block can sit in are needed
+                alg_read = B * (sum(64 * min(N, 64 * (kb + 1)) for kb in range((N + 63) // 64)) * 4.0 + 16.0 * N)
 
-        # ---- roofline: the SAME step sequence once more, the library bracketing its HBM-bound launches with events ----
-        def collect(slot):
-            ms, n = ctypes.c_double(0.0), ctypes.c_int(0)
-            check(lib.gnms_profile_collect(slot, ctypes.byref(ms), ctypes.byref(n)), "profile_collect")
-            return ms.value, n.value
+            # ---- roofline: the SAME step sequence once more, the library bracketing its HBM-bound launches with events ----
+            def collect(slot):
+                ms, n = ctypes.c_double(0.0), ctypes.c_int(0)
+                check(lib.gnms_profile_collect(slot, ctypes.byref(ms), ctypes.byref(n)), "profile_collect")
+                return ms.value, n.value
 
-        # (N > 1 ranks: the other ranks sit in the final barrier while rank 0 is in here -- a short event collection, no ceiling streams)
-        k_roof = max(50, min(args.steps, 200)) if world == 1 else max(5, min(args.steps, 20))
-        for _ in range(3):
-            eager_step()
-        torch.cuda.synchronize()
-        check(lib.gnms_profile_events(1), "profile_events")
-        for _ in range(k_roof):
-            eager_step()
-        torch.cuda.synchronize()
-        check(lib.gnms_profile_events(0), "profile_events")
-        ms_write, n_write = collect(0)
-        ms_read, n_read = collect(1)
-
-        # achievable ceilings: a plain non-temporal store / load stream over the same rotating buffers
-        def stream_rate(fn, nbytes):
-            # timed like the kernel it is the ceiling of: the dispatch's own begin / end timestamps (slot 2), launch gaps excluded
-            for _ in range(2):
-                fn(next_buf())
+            # (N > 1 ranks: the other ranks sit in the final barrier while rank 0 is in here -- a short event collection, no ceiling streams)
+            k_roof = max(50, min(args.steps, 200)) if world == 1 else max(5, min(args.steps, 20))
+            for _ in range(3):
+                eager_step()
             torch.cuda.synchronize()
-            collect(2)
-            check(lib.gnms_profile_events(1), "gnms_profile_events")
-            for _ in range(max(6, 2 * n_buf)):
-                fn(next_buf())
+            check(lib.gnms_profile_events(1), "profile_events")
+            for _ in range(k_roof):
+                eager_step()
             torch.cuda.synchronize()
-            check(lib.gnms_profile_events(0), "gnms_profile_events")
-            ms, n = collect(2)
-            return nbytes * n / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-        sink = torch.zeros(4, dtype=torch.float32, device=dev)
-        n_fl = B * N * N // 4 * 4
-        fill_gbs = stream_rate(lambda b: check(lib.gnms_profile_fill(ptr(b), n_fl, stream_ptr(dev)), "fill"), 4.0 * n_fl) if (n_fl and world == 1) else 0.0
-        fill_what = "plain non-temporal float4 store stream (gnms_profile_fill)"
-        for rows_, nt_ in ((8, 1), (16, 1), (8, 0), (16, 0)):   # the same stream in the writers' geometry; the best of the five is the ceiling
-            if N % rows_ == 0 and N >= 256 and world == 1:
-                tiles_gbs = stream_rate(lambda b: check(lib.gnms_profile_fill_tiles(ptr(b), B, N, N, rows_, nt_, stream_ptr(dev)), "fill_tiles"), 4.0 * B * N * N)
-                if tiles_gbs > fill_gbs:
-                    fill_gbs = tiles_gbs
-                    fill_what = "plain %s store stream, persistent 16-wave workgroups, %d rows x 1 KiB per wave (gnms_profile_fill_tiles)" % (
-                        "non-temporal" if nt_ else "16-byte", rows_)
-        read_gbs = 0.0
-        if n_fl and world == 1:
-            for b_ in iou_bufs:
-                b_.fill_(0.25)
-            read_gbs = stream_rate(lambda b: check(lib.gnms_profile_read(ptr(b), n_fl, ptr(sink), stream_ptr(dev)), "read"), 4.0 * n_fl)
+            check(lib.gnms_profile_events(0), "profile_events")
+            ms_write, n_write = collect(0)
+            ms_read, n_read = collect(1)
 
-        pmc, pmc_note = {}, None
-        workload_args = ["--boxes", str(N), "--batch", str(B), "--kind", args.kind, "--dim", str(args.dim)] + (["--two-calls"] if args.two_calls else []) + (
-            ["--sorted-scores"] if args.sorted_scores else [])
-        if args.pmc_summary:
-            with open(args.pmc_summary) as f:
-                pmc = json.load(f).get("traffic_bytes_per_launch", {})
-            pmc_note = "tools/pmc.sh, " + args.pmc_summary
-        elif world == 1 and not args.no_extras and not args.graph:
-            try:
-                pmc, pmc_note = _pmc_traffic(workload_args, B, N)
-            except Exception as e:                            # the counters are evidence beside the line, never a reason to lose it
-                pmc, pmc_note = {}, "PMC pass failed: %s" % (str(e)[:200],)
+            # achievable ceilings: a plain non-temporal store / load stream over the same rotating buffers
+            def stream_rate(fn, nbytes):
+                # timed like the kernel it is the ceiling of: the dispatch's own begin / end timestamps (slot 2), launch gaps excluded
+                for _ in range(2):
+                    fn(next_buf())
+                torch.cuda.synchronize()
+                collect(2)
+                check(lib.gnms_profile_events(1), "gnms_profile_events")
+                for _ in range(max(6, 2 * n_buf)):
+                    fn(next_buf())
+                torch.cuda.synchronize()
+                check(lib.gnms_profile_events(0), "gnms_profile_events")
+                ms, n = collect(2)
+                return nbytes * n / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+            sink = torch.zeros(4, dtype=torch.float32, device=dev)
+            n_fl = B * N * N // 4 * 4
+            fill_gbs = stream_rate(lambda b: check(lib.gnms_profile_fill(ptr(b), n_fl, stream_ptr(dev)), "fill"), 4.0 * n_fl) if (n_fl and world == 1) else 0.0
+            fill_what = "plain non-temporal float4 store stream (gnms_profile_fill)"
+            for rows_, nt_ in ((8, 1), (16, 1), (8, 0), (16, 0)):   # the same stream in the writers' geometry; the best of the five is the ceiling
+                if N % rows_ == 0 and N >= 256 and world == 1:
+                    tiles_gbs = stream_rate(lambda b: check(lib.gnms_profile_fill_tiles(ptr(b), B, N, N, rows_, nt_, stream_ptr(dev)), "fill_tiles"), 4.0 * B * N * N)
+                    if tiles_gbs > fill_gbs:
+                        fill_gbs = tiles_gbs
+                        fill_what = "plain %s store stream, persistent 16-wave workgroups, %d rows x 1 KiB per wave (gnms_profile_fill_tiles)" % (
+                            "non-temporal" if nt_ else "16-byte", rows_)
+            read_gbs = 0.0
+            if n_fl and world == 1:
+                for b_ in iou_bufs:
+                    b_.fill_(0.25)
+                read_gbs = stream_rate(lambda b: check(lib.gnms_profile_read(ptr(b), n_fl, ptr(sink), stream_ptr(dev)), "read"), 4.0 * n_fl)
 
-        def roof(ms_sum, launches, nbytes_per_step, kname, ceiling, what):
-            if launches == 0 or ms_sum <= 0:
-                return None
-            per_step_ms = ms_sum / k_roof
-            ach = nbytes_per_step / (per_step_ms * 1e-3) / 1e9
-            return {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
-                    "traffic": (round(pmc[kname]) if kname in pmc else None), "traffic_source": pmc_note, "algorithmic_bytes": round(nbytes_per_step),
-                    "kernel": kname, "kernel_ms": round(per_step_ms, 4), "launches_per_step": round(launches / k_roof, 2),
-                    "ceiling": ({"what": what, "GB/s": round(ceiling, 1), "frac_of_ceiling": round(ach / ceiling, 4)} if ceiling else None),
-                    "measured": "HIP events around the launch inside %d repetitions of the timed step sequence, %d rotating %d-MiB matrix buffers"
-                                % (k_roof, n_buf, mat_bytes >> 20)}
+            pmc, pmc_note = {}, None
+            workload_args = ["--boxes", str(N), "--batch", str(B), "--kind", args.kind, "--dim", str(args.dim)] + (["--two-calls"] if args.two_calls else []) + (
+                ["--sorted-scores"] if args.sorted_scores else [])
+            if args.pmc_summary:
+                with open(args.pmc_summary) as f:
+                    pmc = json.load(f).get("traffic_bytes_per_launch", {})
+                pmc_note = "tools/pmc.sh, " + args.pmc_summary
+            elif world == 1 and not args.no_extras and not args.graph:
+                try:
+                    pmc, pmc_note = _pmc_traffic(workload_args, B, N)
+                except Exception as e:                            # the counters are evidence beside the line, never a reason to lose it
+                    pmc, pmc_note = {}, "PMC pass failed: %s" % (str(e)[:200],)
 
-        if one_call:
-            wname = lib.gnms_profile_write_kernel_name(args.dim, B, N).decode()
-        else:
-            # gnms_iou2d of a box set with itself: the staged writers as a launch of their own up to N = 4096 (iou2d_self_kernel) when the
-            # batch has enough units, the large-matrix writers above (write_staged_kernel)
-            self_ok = N <= 4096 and B <= 127 and B * ((N + 7) // 8) >= 8 * 256
-            wname = ("iou2d_self_kernel" if self_ok else ("write_staged_kernel" if N > 4096 and N % 4 == 0 else "iou2d_kernel")) if args.dim == 2 else "iou3d_sym_kernel"
-        r_write = roof(ms_write, n_write, alg_write, wname, fill_gbs, fill_what)
-        r_read = roof(ms_read, n_read, alg_read, "one_launch_kernel" if N <= 1024 and os.environ.get("GNMS_ONE_LAUNCH", "1") != "0" else "bitmask_kernel", read_gbs, "plain non-temporal float4 load stream (gnms_profile_read)")
+            def roof(ms_sum, launches, nbytes_per_step, kname, ceiling, what):
+                if launches == 0 or ms_sum <= 0:
+                    return None
+                per_step_ms = ms_sum / k_roof
+                ach = nbytes_per_step / (per_step_ms * 1e-3) / 1e9
+                return {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
+                        "traffic": (round(pmc[kname]) if kname in pmc else None), "traffic_source": pmc_note, "algorithmic_bytes": round(nbytes_per_step),
+                        "kernel": kname, "kernel_ms": round(per_step_ms, 4), "launches_per_step": round(launches / k_roof, 2),
+                        "ceiling": ({"what": what, "GB/s": round(ceiling, 1), "frac_of_ceiling": round(ach / ceiling, 4)} if ceiling else None),
+                        "measured": "HIP events around the launch inside %d repetitions of the timed step sequence, %d rotating %d-MiB matrix buffers"
+                                    % (k_roof, n_buf, mat_bytes >> 20)}
+
+            if one_call:
+                wname = lib.gnms_profile_write_kernel_name(args.dim, B, N).decode()
+            else:
+                # gnms_iou2d of a box set with itself: the staged writers as a launch of their own up to N = 4096 (iou2d_self_kernel) when the
+                # batch has enough units, the large-matrix writers above (write_staged_kernel)
+                self_ok = N <= 4096 and B <= 127 and B * ((N + 7) // 8) >= 8 * 256
+                wname = ("iou2d_self_kernel" if self_ok else ("write_staged_kernel" if N > 4096 and N % 4 == 0 else "iou2d_kernel")) if args.dim == 2 else "iou3d_sym_kernel"
+            r_write = roof(ms_write, n_write, alg_write, wname, fill_gbs, fill_what)
+            r_read = roof(ms_read, n_read, alg_read, "one_launch_kernel" if N <= 1024 and os.environ.get("GNMS_ONE_LAUNCH", "1") != "0" else "bitmask_kernel", read_gbs, "plain non-temporal float4 load stream (gnms_profile_read)")
 
         total_boxes = world * B * N * args.steps
         value = total_boxes / dt

@@ -623,8 +623,85 @@ def main():
         print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KiB")
 
 
+# the cases of tests/test_oracle_vs_reference.py (its parametrisation repeats these tables): (seed, N, generator, kwargs)
+VS_REF_2D = [
+    (101, 37, "uniform", {}),
+    (102, 129, "clustered", {}),
+    (103, 300, "clustered", dict(nms_threshold=0.55, group_size=3)),
+    (104, 200, "uniform", dict(pruning_method="sigmoidal", temperature=0.1)),
+    (105, 160, "clustered", dict(pruning_method="soft_nms", temperature=0.3, valid_box_prob_threshold=0.1)),
+    (106, 150, "clustered", dict(mask_group_boxes=False)),
+    (107, 120, "clustered", dict(group_boxes=False)),
+    (108, 257, "clustered", dict(return_sorted_prob=True, nms_threshold=0.3)),
+    (109, 2, "uniform", {}),
+    (110, 1, "uniform", {}),
+]
+VS_REF_3D = [(201, 23, False), (202, 96, True), (203, 170, True)]
+VS_REF_CLASSIC = [(301, 1, "uniform"), (302, 75, "clustered"), (303, 400, "clustered"), (304, 250, "uniform")]
+VS_REF_SOFT_SORT = [(401, 12, 0.01), (402, 33, 0.002), (403, 64, 0.001)]
+
+
+def make_oracle_vs_reference():
+    """oracle_vs_reference.npz: inputs drawn from the case's seed and what the reference computes on them, keyed '<seed>/<field>'.
+    2D: lib/core.py:480 iou and lib/groomed_nms.py:10 differentiable_nms with autograd (dL/dprob = w); 3D: lib/math_3d.py
+    get_corners_of_cuboid and lib/core.py:352 iou3d_approximate, both methods, square and rectangular; lib/nms/py_cpu_nms.py:10 and
+    lib/nms_others.py:119 girshick_nms; lib/groomed_nms.py:131 soft_sort on score-sorted inputs."""
+    out = {}
+    for seed, n, kind, kw in VS_REF_2D:
+        rng = np.random.default_rng(seed)
+        boxes = uniform_boxes_2d(rng, n) if kind == "uniform" else clustered_boxes_2d(rng, n, per=12)
+        scores = tie_free_scores(rng, n)
+        w = rng.uniform(-1.0, 2.0, size=n).astype(np.float32)
+        bt = torch.from_numpy(boxes)
+        iou = core.iou(bt, bt).float()
+        st = torch.from_numpy(scores).clone().requires_grad_(True)
+        valid, invalid, prob = gn.differentiable_nms(st, iou, **kw)
+        (prob * torch.from_numpy(w)).sum().backward()
+        k = "%d/" % seed
+        out.update({k + "boxes": boxes, k + "scores": scores, k + "w": w, k + "iou": iou.numpy(), k + "prob": prob.detach().numpy(),
+                    k + "grad_scores": st.grad.numpy(), k + "valid": np.asarray(valid, np.int64), k + "invalid": np.asarray(invalid, np.int64)})
+    for seed, n, clustered in VS_REF_3D:
+        rng = np.random.default_rng(seed)
+        p = boxes_3d(rng, n, clustered=clustered)
+        corners = math_3d.get_corners_of_cuboid(*[torch.from_numpy(np.ascontiguousarray(p[:, i])) for i in range(7)])
+        k = "%d/" % seed
+        out.update({k + "params": p, k + "corners": corners.numpy().astype(np.float32)})
+        for method in ("normal", "generalized"):
+            # iou3d_approximate mutates its inputs (lib/core.py:379-380): clones
+            bev, i3 = core.iou3d_approximate(corners.clone(), corners.clone(), mode="combinations", method=method)
+            out.update({k + method + "/bev": bev.numpy(), k + method + "/iou3d": i3.numpy()})
+        q = boxes_3d(rng, 11, clustered=True)
+        cb = math_3d.get_corners_of_cuboid(*[torch.from_numpy(np.ascontiguousarray(q[:, i])) for i in range(7)])
+        bev, i3 = core.iou3d_approximate(corners.clone(), cb.clone(), mode="combinations", method="generalized")
+        out.update({k + "corners_b": cb.numpy().astype(np.float32), k + "rect/bev": bev.numpy(), k + "rect/iou3d": i3.numpy()})
+    for seed, n, kind in VS_REF_CLASSIC:
+        rng = np.random.default_rng(seed)
+        b = uniform_boxes_2d(rng, n) if kind == "uniform" else clustered_boxes_2d(rng, n, per=8)
+        dets = np.concatenate([b, tie_free_scores(rng, n)[:, None]], 1).astype(np.float32)
+        k = "%d/" % seed
+        out[k + "dets"] = dets
+        for thr in (0.3, 0.5, 0.75):
+            out[k + "py_cpu_nms/%g" % thr] = np.asarray([int(i) for i in pcn.py_cpu_nms(dets.copy(), thr)], np.int64)
+            for shift in (0, 1):
+                out[k + "girshick_nms/%g/%d" % (thr, shift)] = np.asarray(
+                    [int(i) for i in nms_others.girshick_nms(dets.copy(), thr, shift=shift)], np.int64)
+    for seed, n, temp in VS_REF_SOFT_SORT:
+        rng = np.random.default_rng(seed)
+        s = np.sort(tie_free_scores(rng, n))[::-1].copy()
+        b = clustered_boxes_2d(rng, n, per=4)
+        m = core.iou(torch.from_numpy(b), torch.from_numpy(b), mode="combinations").numpy()
+        ss, C, sm = gn.soft_sort(torch.from_numpy(s), full_matrix=torch.from_numpy(m), temperature=temp)
+        k = "%d/" % seed
+        out.update({k + "scores": s, k + "iou": m, k + "soft_scores": ss.numpy(), k + "perm": C.numpy(), k + "soft_iou": sm.numpy()})
+    np.savez_compressed(os.path.join(OUT, "oracle_vs_reference.npz"), **out)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "f64site":      # only the float64 call-site fixture (independent RNG stream)
+    if len(sys.argv) > 1 and sys.argv[1] == "oracle_vs_reference":      # only that fixture (every case its own seed)
+        torch.manual_seed(0)
+        make_oracle_vs_reference()
+        print("oracle_vs_reference.npz", os.path.getsize(os.path.join(OUT, "oracle_vs_reference.npz")) // 1024, "KiB")
+    elif len(sys.argv) > 1 and sys.argv[1] == "f64site":      # only the float64 call-site fixture (independent RNG stream)
         torch.manual_seed(0)
         torch.set_num_threads(4)
         make_f64_call_site()

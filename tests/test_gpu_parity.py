@@ -1797,7 +1797,7 @@ def test_n_rank_launcher_end_to_end():
         assert len(lines) == 1, r.stdout[-3000:]
         return json.loads(lines[0])
 
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], env=env,
                        capture_output=True, text=True, timeout=900)
     d = one_json_line(r)
     import re
@@ -1810,7 +1810,7 @@ def test_n_rank_launcher_end_to_end():
     assert set(d["box_counts"]) == {"N256", "N1024", "N16384"} and all(v.get("value", 0) > 0 for v in d["box_counts"].values()), d["box_counts"]
     # C5's shape exactly as the driver's 8-GPU run would start it: 8 ranks x 8 images x 16384 cuboids, folded onto this GPU
     r5 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dim", "3", "--boxes", "16384", "--batch", "8", "--steps", "2",
-                         "--warmup", "1"], env=dict(env, GNMS_BENCH_PREWARM="2"), capture_output=True, text=True, timeout=1500)
+                         "--warmup", "1", "--full"], env=dict(env, GNMS_BENCH_PREWARM="2"), capture_output=True, text=True, timeout=1500)
     d5 = one_json_line(r5)
     waits5 = [float(x) for x in re.findall(r"rank \d+ waited ([0-9.]+) s in the final barrier", r5.stderr)]
     assert len(waits5) == 8 and max(waits5) < 60.0, r5.stderr[-2000:]
@@ -1902,7 +1902,7 @@ def test_lazy_index_lists(G, O):
 
 
 def test_bench_line_contract_on_a_small_problem():
-    """bench.py end to end on a small problem (2 images x 512 boxes, a few steps): one JSON line with the driver's fields, the
+    """bench.py --full end to end on a small problem (2 images x 512 boxes, a few steps): one JSON line with the driver's fields, the
     roofline object measured from the library's launch events, parity 0 against the oracle, the CPU baseline -- 2D, 3D and the
     matrix-in variant."""
     import json, os, subprocess, sys
@@ -1910,7 +1910,7 @@ def test_bench_line_contract_on_a_small_problem():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     for extra in ([], ["--dim", "3"], ["--two-calls"], ["--graph", "--no-cpu-baseline"]):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--boxes", "512", "--batch", "2", "--steps", "4", "--warmup", "1",
-                            "--cpu-seconds", "0.3", "--no-extras"] + extra, env=env, capture_output=True, text=True, timeout=900)
+                            "--cpu-seconds", "0.3", "--full", "--no-extras"] + extra, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         d = json.loads(r.stdout.strip().splitlines()[-1])
         for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
@@ -1925,6 +1925,50 @@ def test_bench_line_contract_on_a_small_problem():
             if "--dim" not in extra:
                 assert d["parity"]["max_abs_dscore"] == 0.0 and d["parity"]["max_abs_dgrad_scores"] == 0.0
             assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] == 1 and d["cpu_baseline"]["value"] > 0
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench.py run prints the headline line and nothing of --full; --dump-outputs writes the last timed step's outputs, the
+    same on a second run, and equal to the CPU oracle on the bench's seeded inputs (eager entry and the replayed HIP graph)."""
+    import json, os, subprocess, sys
+    from groomed_nms_amd import synthetic
+    from oracle import oracle as O
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    B, N = 2, 512
+
+    def run(tag, extra=()):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--boxes", str(N), "--batch", str(B), "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / tag)] + list(extra), env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0]), {f[:-4]: np.load(tmp_path / tag / f) for f in os.listdir(tmp_path / tag)}
+
+    d, a = run("a")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "boxes/s" and d["dtype"] == "f32"
+    for key in ("parity", "cpu_baseline", "other_kind", "hip_graph_replay", "spread", "two_calls", "N256"):
+        assert key not in d, key
+    assert d["roofline"] is None
+    assert set(a) == {"prob", "grad_scores", "order", "valid", "invalid", "num_valid", "num_invalid", "iou"}
+    assert a["prob"].dtype == np.float32 and a["prob"].shape == (B, N) and a["iou"].shape == (B, N, N) and a["valid"].dtype == np.float64
+    _, b = run("b")
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    boxes, scores = synthetic.batch_2d(1000, B, N, "uniform")
+    w = np.linspace(-1.0, 2.0, N).astype(np.float32)
+    _, g = run("graph", ["--graph"])
+    assert set(g) == {"prob", "grad_scores", "iou"}
+    for i in range(B):
+        m = O.iou2d(boxes[i], boxes[i])
+        ref = O.differentiable_nms(scores[i], m, grad_prob=w)
+        for got in (a, g):
+            assert np.array_equal(got["iou"][i], m, equal_nan=True)
+            assert np.array_equal(got["prob"][i], ref["prob"]) and np.array_equal(got["grad_scores"][i], ref["grad_scores"])
+        nv = int(a["num_valid"][i])
+        assert set(a["valid"][i, :nv].astype(np.int64).tolist()) == set(ref["valid"].tolist())
 
 
 def test_profile_hooks(G):

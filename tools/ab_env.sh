@@ -4,7 +4,7 @@ VAR=$1; VALS=$2; shift 2
 for rep in 1 2; do for v in $VALS; do
   for kind in ${KINDS:-clustered uniform}; do
   echo -n "$VAR=$v $kind "
-  env $VAR=$v python bench.py --steps 100 --warmup 5 --kind $kind --no-other-kind --no-extras --no-cpu-baseline "$@" 2>/dev/null | python -c "
+  env $VAR=$v python bench.py --full --steps 100 --warmup 5 --kind $kind --no-other-kind --no-extras --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     l=l.strip()

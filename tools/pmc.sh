@@ -6,6 +6,7 @@
 # -> doubled; WRITE_SIZE is calibrated in the same run on gnms_profile_fill's known store stream (prof_fill_kernel writes exactly
 # 4*B*N*N bytes per launch) and scaled by that factor.
 TAG=$1; shift
+set -- --full "$@"          # the roofline stage runs prof_fill_kernel, the WRITE_SIZE calibration below
 export TMPDIR=/tmp
 R=$PWD
 for C in FETCH_SIZE WRITE_SIZE; do

@@ -15,7 +15,7 @@ O=gpurun_out/profiles_$T
 mkdir -p $O
 bash tools/pmc.sh $T > $O/pmc_stdout.txt 2>&1
 cp gpurun_out/pmc_${T}_summary.json $O/${T}_pmc_summary.json
-python bench.py --steps 200 --warmup 20 --pmc-summary $O/${T}_pmc_summary.json > $O/${T}_bench.json 2> $O/bench.err
+python bench.py --full --steps 200 --warmup 20 --pmc-summary $O/${T}_pmc_summary.json > $O/${T}_bench.json 2> $O/bench.err
 bash tools/prof.sh ${T}_main --steps 200 --warmup 20 --no-cpu-baseline --no-other-kind > $O/prof_main.txt 2>&1
 cp gpurun_out/prof_${T}_main/bench_kernel_stats.csv $O/${T}_bench_kernel_stats.csv
 tail -1 gpurun_out/prof_${T}_main/bench_stdout.txt > $O/${T}_bench_under_rocprof.json
@@ -39,14 +39,14 @@ tail -1 gpurun_out/prof_${T}_clu/bench_stdout.txt > $O/${T}_clustered4096_bench_
 : > $O/${T}_grid.jsonl
 for n in 256 1024 4096 16384; do for k in clustered uniform; do
   st=100; [ $n -ge 16384 ] && st=30
-  python bench.py --boxes $n --kind $k --steps $st --warmup 10 --no-cpu-baseline --no-other-kind 2>/dev/null | tail -1 >> $O/${T}_grid.jsonl
+  python bench.py --full --boxes $n --kind $k --steps $st --warmup 10 --no-cpu-baseline --no-other-kind 2>/dev/null | tail -1 >> $O/${T}_grid.jsonl
 done; done
 for n in 4096 16384; do for k in clustered uniform; do
   st=100; [ $n -ge 16384 ] && st=30
-  python bench.py --dim 3 --boxes $n --kind $k --steps $st --warmup 10 --no-cpu-baseline --no-other-kind 2>/dev/null | tail -1 >> $O/${T}_grid.jsonl
+  python bench.py --full --dim 3 --boxes $n --kind $k --steps $st --warmup 10 --no-cpu-baseline --no-other-kind 2>/dev/null | tail -1 >> $O/${T}_grid.jsonl
 done; done
-python bench.py --two-calls --kind uniform --steps 100 --warmup 10 --no-other-kind --cpu-seconds 3 2>/dev/null | tail -1 > $O/${T}_two_calls_bench.json
-for n in 512 1024 2048; do python bench.py --graph --kind clustered --boxes $n --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/${T}_graph.jsonl; done
+python bench.py --full --two-calls --kind uniform --steps 100 --warmup 10 --no-other-kind --cpu-seconds 3 2>/dev/null | tail -1 > $O/${T}_two_calls_bench.json
+for n in 512 1024 2048; do python bench.py --full --graph --kind clustered --boxes $n --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/${T}_graph.jsonl; done
 python tools/kernel_times.py > $O/${T}_kernel_times.txt 2>/dev/null
 python tools/kernel_times.py --boxes 16384 --reps 10 >> $O/${T}_kernel_times.txt 2>/dev/null
 python tools/small_n.py 2>/dev/null | grep "^{" > $O/${T}_small_n.jsonl
