@@ -451,7 +451,25 @@ __global__ __launch_bounds__(256) void sgemm_reduce_kernel(const float* __restri
 // (small or odd shapes, a stream that is being captured, a process without the libraries) and behind gnms_profile_sgemm for comparison.
 // Resolved with dlopen / dlsym at first use -- libgroomed_nms_hip.so has no link-time dependency on it; inside a PyTorch process the name
 // resolves to the copy PyTorch has already mapped.  One handle per device, created once; atomics off (deterministic sums).
+// A library's handle (and hipBLASLt's workspace) serves every stream of its device, and the mutex only covers the enqueue: products of
+// one library are therefore chained across streams like the top-K path's cooperative launches -- one event per device, recorded behind
+// every product; a product on another stream than the last one waits for it first (products of one stream are ordered anyway).
 // ------------------------------------------------------------------------------------------------
+struct VendorChain {
+    hipEvent_t ev[64] = {};
+    hipStream_t last[64] = {};
+    bool any[64] = {};
+    // before the enqueue on `st` (the library's mutex held): order the product behind the previous one of this device
+    bool before(int dev, hipStream_t st) {
+        if (!ev[dev] && hipEventCreateWithFlags(&ev[dev], hipEventDisableTiming) != hipSuccess) { ev[dev] = nullptr; return false; }
+        return !(any[dev] && last[dev] != st) || hipStreamWaitEvent(st, ev[dev], 0) == hipSuccess;
+    }
+    // after a successful enqueue
+    void after(int dev, hipStream_t st) {
+        if (hipEventRecord(ev[dev], st) == hipSuccess) { last[dev] = st; any[dev] = true; }
+        else (void)hipStreamSynchronize(st);                          // (no event: the next product of any stream then finds this one done)
+    }
+};
 struct RocblasApi {
     typedef int (*create_t)(void**);
     typedef int (*set_stream_t)(void*, hipStream_t);
@@ -462,6 +480,7 @@ struct RocblasApi {
     set_atomics_t set_atomics = nullptr;
     sgemm_t sgemm = nullptr;
     void* handle[64] = {};
+    VendorChain chain;
     std::mutex mu;
     bool tried = false, ok = false;
 };
@@ -498,9 +517,12 @@ bool rocblas_sgemm_rowmajor(const float* A, const float* B, float* D, int M, int
         R.handle[dev] = hd;
     }
     if (R.set_stream(R.handle[dev], st) != 0) return false;
+    if (!R.chain.before(dev, st)) return false;
     // row-major D = A B  ==  column-major D^T = B^T A^T: (N x M) = (N x K)(K x M), operands swapped, no transposes
     const float alpha = 1.0f, beta = accumulate ? 1.0f : 0.0f;
-    return R.sgemm(R.handle[dev], 111, 111, N, M, K, &alpha, B, (int)ldb, A, (int)lda, &beta, D, (int)ldd) == 0;   // 111 = rocblas_operation_none
+    if (R.sgemm(R.handle[dev], 111, 111, N, M, K, &alpha, B, (int)ldb, A, (int)lda, &beta, D, (int)ldd) != 0) return false;   // 111 = rocblas_operation_none
+    R.chain.after(dev, st);
+    return true;
 }
 
 // hipBLASLt, the library behind torch.matmul on this platform: ahead of rocBLAS's own sgemm and of the kernels here from 2048^3 on
@@ -517,9 +539,10 @@ struct LtApi {
     decltype(&hipblasLtMatmul) matmul = nullptr;
     decltype(&hipblasLtMatmulDescDestroy) desc_destroy = nullptr;
     decltype(&hipblasLtMatrixLayoutDestroy) layout_destroy = nullptr;
-    struct Plan { hipblasLtMatmulDesc_t desc; hipblasLtMatrixLayout_t a, b, d; hipblasLtMatmulAlgo_t algo; size_t ws; };
+    struct Plan { hipblasLtMatmulDesc_t desc; hipblasLtMatrixLayout_t a, b, d; hipblasLtMatmulAlgo_t algo; size_t ws; bool ok; };
     hipblasLtHandle_t handle[64] = {};
     void* wsp[64] = {};
+    VendorChain chain;
     hipblasLtMatmulPreference_t pref = nullptr;
     std::map<std::array<int64_t, 7>, Plan> plans;
     std::mutex mu;
@@ -569,32 +592,46 @@ bool hipblaslt_sgemm_rowmajor(const float* A, const float* B, float* D, int M, i
         R.wsp[dev] = w;
     }
     const std::array<int64_t, 7> key = {(int64_t)dev, M, N, K, lda, ldb, ldd};
+    auto release = [&](LtApi::Plan& P) {
+        if (R.desc_destroy && P.desc) (void)R.desc_destroy(P.desc);
+        if (R.layout_destroy) {
+            for (hipblasLtMatrixLayout_t l : {P.a, P.b, P.d})
+                if (l) (void)R.layout_destroy(l);
+        }
+        P.desc = nullptr; P.a = P.b = P.d = nullptr;
+    };
     auto it = R.plans.find(key);
     if (it == R.plans.end()) {
         if (R.plans.size() >= 256) {                                  // (a caller that walks through many shapes: the cache starts over instead of growing)
-            for (auto& kv : R.plans) {
-                if (R.desc_destroy) (void)R.desc_destroy(kv.second.desc);
-                if (R.layout_destroy) { (void)R.layout_destroy(kv.second.a); (void)R.layout_destroy(kv.second.b); (void)R.layout_destroy(kv.second.d); }
-            }
+            for (auto& kv : R.plans) release(kv.second);
             R.plans.clear();
         }
         LtApi::Plan P{};
         // column-major: "A" = B^T as stored (N x K, ld ldb), "B" = A^T as stored (K x M, ld lda), C = D = D^T as stored (N x M, ld ldd)
-        if (R.desc_create(&P.desc, HIPBLAS_COMPUTE_32F, HIP_R_32F) != HIPBLAS_STATUS_SUCCESS ||
-            R.layout_create(&P.a, HIP_R_32F, (uint64_t)N, (uint64_t)K, ldb) != HIPBLAS_STATUS_SUCCESS ||
-            R.layout_create(&P.b, HIP_R_32F, (uint64_t)K, (uint64_t)M, lda) != HIPBLAS_STATUS_SUCCESS ||
-            R.layout_create(&P.d, HIP_R_32F, (uint64_t)N, (uint64_t)M, ldd) != HIPBLAS_STATUS_SUCCESS) return false;
         hipblasLtMatmulHeuristicResult_t res[1];
         int got = 0;
-        if (R.heuristic(R.handle[dev], P.desc, P.a, P.b, P.d, P.d, R.pref, 1, res, &got) != HIPBLAS_STATUS_SUCCESS || got < 1 ||
-            res[0].state != HIPBLAS_STATUS_SUCCESS || res[0].workspaceSize > kLtWorkspace) return false;
-        P.algo = res[0].algo;
-        P.ws = res[0].workspaceSize;
+        P.ok = R.desc_create(&P.desc, HIPBLAS_COMPUTE_32F, HIP_R_32F) == HIPBLAS_STATUS_SUCCESS &&
+               R.layout_create(&P.a, HIP_R_32F, (uint64_t)N, (uint64_t)K, ldb) == HIPBLAS_STATUS_SUCCESS &&
+               R.layout_create(&P.b, HIP_R_32F, (uint64_t)K, (uint64_t)M, lda) == HIPBLAS_STATUS_SUCCESS &&
+               R.layout_create(&P.d, HIP_R_32F, (uint64_t)N, (uint64_t)M, ldd) == HIPBLAS_STATUS_SUCCESS &&
+               R.heuristic(R.handle[dev], P.desc, P.a, P.b, P.d, P.d, R.pref, 1, res, &got) == HIPBLAS_STATUS_SUCCESS && got >= 1 &&
+               res[0].state == HIPBLAS_STATUS_SUCCESS && res[0].workspaceSize <= kLtWorkspace;
+        if (P.ok) {
+            P.algo = res[0].algo;
+            P.ws = res[0].workspaceSize;
+        } else {
+            release(P);                                               // a refused shape is remembered: no handles kept, no second heuristic query
+        }
         it = R.plans.emplace(key, P).first;
     }
     const LtApi::Plan& P = it->second;
+    if (!P.ok) return false;
+    if (!R.chain.before(dev, st)) return false;
     const float alpha = 1.0f, beta = accumulate ? 1.0f : 0.0f;
-    return R.matmul(R.handle[dev], P.desc, &alpha, B, P.a, A, P.b, &beta, D, P.d, D, P.d, &P.algo, R.wsp[dev], kLtWorkspace, st) == HIPBLAS_STATUS_SUCCESS;
+    if (R.matmul(R.handle[dev], P.desc, &alpha, B, P.a, A, P.b, &beta, D, P.d, D, P.d, &P.algo, R.wsp[dev], kLtWorkspace, st) != HIPBLAS_STATUS_SUCCESS)
+        return false;
+    R.chain.after(dev, st);
+    return true;
 }
 
 // variant: 0 = the product path (hipBLASLt from 2048^3 on, rocBLAS from 512^3 on, else -- and whenever a library is missing -- the kernels
@@ -611,10 +648,15 @@ int launch_sgemm(const float* A, const float* B, float* D, int M, int N, int K, 
         if (rocblas_sgemm_rowmajor(A, B, D, M, N, K, lda, ldb, ldd, accumulate, st)) return GNMS_OK;
         if (variant == 2) { gnms_set_error("gnms_profile_sgemm: rocBLAS is not available"); return GNMS_ERR_UNSUPPORTED; }
     }
+    // No split K on a stream that is being captured: its partial panels would be an allocation inside the graph (a memory node), and a
+    // captured soft sort at 1024^3 gave a wrong product on its second replay with them (tests/test_soft_sort_at_scale.py).  Unsplit, a
+    // captured product is kernels only, writing straight into D.
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
     const bool aligned = (lda % 4 == 0) && (ldb % 4 == 0) && ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0);
     if (aligned && M % GM == 0 && N % GN == 0 && K % (2 * GK) == 0 && K >= 2 * GK) {
         const long big_tiles = (long)(M / GM) * (N / GN);
-        if (big_tiles >= 256) {
+        if (big_tiles >= 256 || capturing) {
             sgemm_mfma_big_kernel<<<dim3(N / GN, M / GM), 256, 0, st>>>(A, B, D, K, (long)lda, (long)ldb, (long)ldd, accumulate, 0L, variant == 3 ? 1 : 0);
             GNMS_CHECK_LAUNCH();
             return GNMS_OK;
@@ -644,7 +686,7 @@ int launch_sgemm(const float* A, const float* B, float* D, int M, int N, int K, 
     const long tiles = (long)grid.x * grid.y;
     const int cus = gnms_device_cu_count();
     int S = 1;
-    while (S < 16 && tiles * S < 2L * cus && K / (2 * S) >= 64) S *= 2;
+    while (!capturing && S < 16 && tiles * S < 2L * cus && K / (2 * S) >= 64) S *= 2;
     if (S > 1) {
         const int kslice = gnms_div_up(gnms_div_up(K, S), BK) * BK;
         S = gnms_div_up(K, kslice);
