@@ -40,6 +40,10 @@ _SIGNATURES = {
                                               ctypes.c_int64, c_vp]),
     "gnms_iou3d_from_params": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                               ctypes.c_int64, c_vp]),
+    "gnms_iou3d_exact": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_int64, c_vp]),
+    "gnms_iou3d_exact_from_params": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                                    ctypes.c_int64, c_vp]),
+    "gnms_iou3d_exact_list_f64": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp]),
     "gnms_nms_overlap3d_from_params": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_vp, ctypes.c_int64, c_vp]),
     "gnms_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(GnmsParams)]),
     "gnms_forward": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, ctypes.POINTER(GnmsParams),

@@ -15,6 +15,7 @@
 #include "iou3d_pair.h"
 #include "iou3d_tile.h"
 #include "iou3d_sym.h"
+#include "cuboid_corners.h"
 
 namespace {
 
@@ -75,24 +76,7 @@ __global__ void aabb_from_corners_kernel(const float* __restrict__ corners, long
     o[2] = make_float4(r[8], r[9], r[10], r[11]);
 }
 
-// get_corners_of_cuboid, lib/math_3d.py:364-435 (same operation order as oracle/gnms_oracle.c)
-__device__ __forceinline__ void corners_of(const float* p, float (&cx)[8], float (&cy)[8], float (&cz)[8]) {
-    const float x = p[0], y = p[1], z = p[2], w = p[3], h = p[4], l = p[5], ry = p[6];
-    const float c = cosf(ry), s = sinf(ry);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const bool xh = (k == 1) | (k == 3) | (k == 5) | (k == 6);   // :401
-        const bool yh = (k == 2) | (k == 3) | (k == 6) | (k == 7);   // :402
-        const bool zh = k >= 4;                                      // :403
-        float bx = (xh ? l : 0.0f) - l / 2;
-        float by = (yh ? h : 0.0f) - h / 2;
-        float bz = (zh ? w : 0.0f) - w / 2;
-        float rx = c * bx + 0.0f * by + s * bz;                      // bmm(R, corners) :430
-        float ryy = 0.0f * bx + 1.0f * by + 0.0f * bz;
-        float rz = (-s) * bx + 0.0f * by + c * bz;
-        cx[k] = rx + x; cy[k] = ryy + y; cz[k] = rz + z;             // :433-435
-    }
-}
+using gnms_geom::corners_of;   // cuboid_corners.h (shared with iou3d_exact.hip)
 
 __global__ void corners_kernel(const float* __restrict__ params, long count, float* __restrict__ corners) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -4,6 +4,7 @@ lib/math_3d.py that feed the NMS.  Same names and argumen
   intersect(box_a, box_b, mode, data_type)           lib/core.py:178-243
   iou3d_approximate(c1, c2, mode, method)            lib/core.py:305-421
   get_corners_of_cuboid(x, y, z, w, h, l, ry)        lib/math_3d.py:364-490
+  iou3d(c1, c2, vol)                                 lib/core.py:246-302 (exact rotated IoU, csrc/iou3d_exact.hip)
 'combinations' mode runs in the HIP kernels (csrc/iou_kernels.hip); 'list' mode is O(N) elementwise
 tensor arithmetic.  ndarray in -> ndarray out.  float64 ndarrays -- what the inference call site passes
 (lib/rpn_util.py:1295: `aboxes` is float64 after the hstack at :1258) -- keep their dtype like the reference's
@@ -18,7 +19,8 @@ from . import _lib
 from ._lib import check, ptr, stream_ptr, on_device
 from .groomed_nms import _device
 
-__all__ = ["iou", "intersect", "iou3d_approximate", "get_corners_of_cuboid", "iou_batched", "iou3d_batched"]
+__all__ = ["iou", "intersect", "iou3d_approximate", "get_corners_of_cuboid", "iou_batched", "iou3d_batched", "iou3d",
+           "iou3d_exact_batched"]
 
 
 def _is_f64_array(x):
@@ -197,3 +199,60 @@ def iou3d_approximate(corners_3d_b1, corners_3d_b2, mode="list", method="normal"
         bev, i3 = iou3d_batched(c1.reshape(n, 1, 3, 8), c2.reshape(n, 1, 3, 8), method=method, want_bev=True)
         return _back(bev.reshape(n), kind, dev), _back(i3.reshape(n), kind, dev)
     raise ValueError('unknown mode {}'.format(mode))
+
+
+def iou3d_exact_batched(a, b=None, from_params=False, volume="box", want_bev=False, out=None):
+    """The exact rotated IoU (lib/core.py:246-302) of every pair: a [B,M,3,8] corners (or [B,M,7] params when from_params), b likewise
+    with N boxes (None: a) -> iou_3d [B,M,N], or (iou_bev, iou_3d) with want_bev.  CUDA fp32 in and out, float64 geometry inside.
+    volume: "box" -- the sum of the boxes' own volumes (footprint area x height); "aabb" -- the sum of their corner AABB volumes, what
+    the reference's iou3d uses when it is given no `vol` (:276-277)."""
+    if volume not in ("box", "aabb"):
+        raise ValueError("unknown volume {}".format(volume))
+    lib = _lib.load()
+    a = a.contiguous()
+    b = a if b is None else b.contiguous()
+    B, M = a.shape[0], a.shape[1]
+    N = b.shape[1]
+    o3 = out if out is not None else torch.empty((B, M, N), dtype=torch.float32, device=a.device)
+    bev = torch.empty((B, M, N), dtype=torch.float32, device=a.device) if want_bev else None
+    fn = lib.gnms_iou3d_exact_from_params if from_params else lib.gnms_iou3d_exact
+    with on_device(a.device):
+        check(fn(ptr(a), ptr(b), B, M, N, 0 if volume == "box" else 1, ptr(bev), ptr(o3), max(N, 1), stream_ptr(a.device)),
+              "gnms_iou3d_exact")
+    return (bev, o3) if want_bev else o3
+
+
+def iou3d(corners_3d_b1, corners_3d_b2, vol=None):
+    """lib/core.py:246-302: (iou_bev, iou_3d) of two cuboids given as (3, 8) corners -- two float64 scalars -- or of K pairs given as
+    (K, 3, 8) arrays, with `vol` None, a scalar or (K,) -- two (K,) arrays.  vol None: the sum of the corner AABB volumes, as in the
+    reference.  The footprints are intersected exactly in float64 on the GPU (gnms_iou3d_exact_list_f64) where the reference calls
+    shapely.  Inputs are not modified.  ndarray in -> ndarray out; a torch tensor in -> a float64 tensor out on its device."""
+    kind = "torch" if torch.is_tensor(corners_3d_b1) else "numpy"
+    out_device = corners_3d_b1.device if kind == "torch" else None
+    dev = out_device if kind == "torch" and out_device.type == "cuda" else _device()
+
+    def dev64(x):
+        if torch.is_tensor(x):
+            return x.detach().to(device=dev, dtype=torch.float64).contiguous()
+        return torch.from_numpy(np.array(x, dtype=np.float64)).to(dev)
+
+    a, b = dev64(corners_3d_b1), dev64(corners_3d_b2)
+    single = a.dim() == 2
+    if single:
+        a, b = a.unsqueeze(0), b.unsqueeze(0)
+    if a.dim() != 3 or tuple(a.shape[1:]) != (3, 8) or a.shape != b.shape:
+        raise ValueError("iou3d: corners must be (3, 8) or (K, 3, 8) and of the same shape, got %s and %s"
+                         % (tuple(corners_3d_b1.shape), tuple(corners_3d_b2.shape)))
+    k = a.shape[0]
+    v = None if vol is None else dev64(vol).reshape(-1).expand(k).contiguous()
+    bev = torch.empty(k, dtype=torch.float64, device=dev)
+    i3 = torch.empty(k, dtype=torch.float64, device=dev)
+    if k:
+        lib = _lib.load()
+        with on_device(dev):
+            check(lib.gnms_iou3d_exact_list_f64(ptr(a), ptr(b), k, ptr(v), ptr(bev), ptr(i3), stream_ptr(dev)), "gnms_iou3d_exact_list_f64")
+    if kind == "torch":
+        bev, i3 = bev.to(out_device), i3.to(out_device)
+        return (bev[0], i3[0]) if single else (bev, i3)
+    bev, i3 = bev.cpu().numpy(), i3.cpu().numpy()
+    return (np.float64(bev[0]), np.float64(i3[0])) if single else (bev, i3)

@@ -107,6 +107,31 @@ int gnms_iou3d_approximate(const float* corners_a, const float* corners_b, int B
 int gnms_iou3d_from_params(const float* params_a, const float* params_b, int B, int M, int N, int method,
                            float* iou_bev, float* iou_3d, int64_t ld, void* stream);
 
+/* iou3d(corners_b1, corners_b2, vol)  lib/core.py:246-302: the EXACT IoU of two rotated cuboids (the reference intersects the
+ * bird's-eye-view footprints with shapely).  Footprint = the quadrilateral of corners 7, 2, 3, 6 in (x, z) (:289-294); y overlap
+ * = max(0, min(ymax) - max(ymin)) over all 8 corners (:282-286);
+ *   iou_bev = I / (area_a + area_b - I),   iou_3d = I * y_overlap / (vol - I * y_overlap)   (:296-300).
+ * Geometry in float64 (as GEOS), no clamping: 0/0 yields NaN like the reference (two zero-area footprints).  Footprints must be
+ * convex quadrilaterals, of either orientation (both corner conventions of the reference give one); non-convex or
+ * self-intersecting quadrilaterals are NOT supported.
+ * corners_a [B][M][3][8], corners_b [B][N][3][8] -> iou_bev, iou_3d [B][M][ld] fp32, ld >= N.  Either output may be NULL, not both.
+ *   volume_mode 0: vol = sum of the boxes' own volumes (|footprint area| * y extent);
+ *               1: vol = sum of the corner AABB volumes, get_volume (:452-456) -- what iou3d uses when vol is None (:276-277).
+ * No allocation: capturable in a graph. */
+int gnms_iou3d_exact(const float* corners_a, const float* corners_b, int B, int M, int N, int volume_mode,
+                     float* iou_bev, float* iou_3d, int64_t ld, void* stream);
+
+/* same, with get_corners_of_cuboid fused as the prologue (the arithmetic of gnms_corners_of_cuboid, hence bit-identical to
+ * gnms_corners_of_cuboid followed by gnms_iou3d_exact): params_a [B][M][7], params_b [B][N][7] = (x, y, z, w, h, l, ry) */
+int gnms_iou3d_exact_from_params(const float* params_a, const float* params_b, int B, int M, int N, int volume_mode,
+                                 float* iou_bev, float* iou_3d, int64_t ld, void* stream);
+
+/* The drop-in's form: `count` pairs (corners_a[i], corners_b[i]), float64 corners [count][3][8] each.  vol: per-pair sums of the
+ * two volumes [count] as the reference's `vol` argument, or NULL = the corner AABB volumes (:276-277).  iou_bev / iou_3d [count]
+ * float64, either may be NULL, not both. */
+int gnms_iou3d_exact_list_f64(const double* corners_a, const double* corners_b, int64_t count, const double* vol,
+                              double* iou_bev, double* iou_3d, void* stream);
+
 /* The matrix both reference callers hand to the NMS in 3D mode: 0.5 * (1 + GIoU3D) of the cuboids' corner AABBs
  * (lib/loss/rpn_3d.py:778-781, lib/rpn_util.py:1309-1312), params3d [B][N][7] -> out [B][N][ld], when the caller knows the
  * threshold the layer will apply.  Same values as gnms_iou3d_from_params(method 2) to within 2e-6, but HBM-write bound instead of
