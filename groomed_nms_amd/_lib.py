@@ -103,6 +103,11 @@ _SIGNATURES = {
     "gnms_best_targets": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_float, c_vp, c_vp,
                                           c_vp, c_vp]),
     "gnms_aploss": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_float, ctypes.c_float, c_vp, c_vp, c_vp]),
+    "gnms_compute_targets_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "gnms_compute_targets": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, c_vp, ctypes.c_int, c_vp,
+                                            c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_int64, c_vp,
+                                            ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 5
+                             + [c_vp] * 8 + [c_vp, ctypes.c_size_t, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

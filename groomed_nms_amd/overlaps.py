@@ -5,6 +5,7 @@ lib/math_3d.py that feed the NMS.  Same names and argumen
   iou3d_approximate(c1, c2, mode, method)            lib/core.py:305-421
   get_corners_of_cuboid(x, y, z, w, h, l, ry)        lib/math_3d.py:364-490
   iou3d(c1, c2, vol)                                 lib/core.py:246-302 (exact rotated IoU, csrc/iou3d_exact.hip)
+  iou_ign(box_a, box_b, mode, data_type)             lib/core.py:535-575 (through gnms_compute_targets, csrc/targets.hip)
 'combinations' mode runs in the HIP kernels (csrc/iou_kernels.hip); 'list' mode is O(N) elementwise
 tensor arithmetic.  ndarray in -> ndarray out.  float64 ndarrays -- what the inference call site passes
 (lib/rpn_util.py:1295: `aboxes` is float64 after the hstack at :1258) -- keep their dtype like the reference's
@@ -20,7 +21,7 @@ from ._lib import check, ptr, stream_ptr, on_device
 from .groomed_nms import _device
 
 __all__ = ["iou", "intersect", "iou3d_approximate", "get_corners_of_cuboid", "iou_batched", "iou3d_batched", "iou3d",
-           "iou3d_exact_batched"]
+           "iou3d_exact_batched", "iou_ign"]
 
 
 def _is_f64_array(x):
@@ -256,3 +257,30 @@ def iou3d(corners_3d_b1, corners_3d_b2, vol=None):
         return (bev[0], i3[0]) if single else (bev, i3)
     bev, i3 = bev.cpu().numpy(), i3.cpu().numpy()
     return (np.float64(bev[0]), np.float64(i3[0])) if single else (bev, i3)
+
+
+def iou_ign(box_a, box_b, mode='combinations', data_type=None):
+    """lib/core.py:535-575: how much of each box_a lies inside each box_b, inter / (area_a + area_b * 0 - inter * 0), as [len(a), len(b)]
+    float64.  NumPy combinations mode, the one compute_targets uses: box_b (the ignore regions) in float64, box_a in its own float32 /
+    float64 for its area.  That is NumPy's result whenever either side is float64; two float32 inputs, which NumPy would keep in
+    float32, are computed the same way (box_b widened) and come back as float64.  Runs the ignore pass of gnms_compute_targets."""
+    if data_type is None:
+        data_type = type(box_a)
+    if mode != 'combinations':
+        raise ValueError('unknown mode {}'.format(mode))
+    if data_type is not np.ndarray:
+        raise TypeError("iou_ign: NumPy arrays only (the reference's combinations mode on ndarrays)")
+    from . import targets
+    a = np.asarray(box_a)
+    a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    b = np.asarray(box_b, dtype=np.float64).reshape(-1, 4)
+    out = np.empty((a.shape[0], b.shape[0]), dtype=np.float64)
+    if out.size == 0:
+        return out
+    dev = _device()
+    ta = torch.from_numpy(np.ascontiguousarray(a[:, :4]))[None].to(dev)
+    for k0 in range(0, b.shape[0], targets.MAX_GTS):
+        tb = torch.from_numpy(np.ascontiguousarray(b[k0:k0 + targets.MAX_GTS]))[None].to(dev)
+        t = targets.compute_targets_batched(ta, None, None, 0.0, 0.0, 0.0, 0.0, 0.0, gts_ign=tb, want=("ols_ign",))
+        out[:, k0:k0 + tb.shape[1]] = t.ols_ign[0].cpu().numpy()
+    return out

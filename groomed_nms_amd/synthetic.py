@@ -71,3 +71,47 @@ def batch_3d(seed, B, N, clustered=True, per=64):
     params = np.stack([boxes_3d(rng, N, clustered, per) for _ in range(B)])
     scores = np.stack([tie_free_scores(rng, N) for _ in range(B)])
     return params, scores
+
+
+def anchor_scene(rng, B, Mmax=256, Kmax=8, dtype=np.float32, D3=16, acols=11, garbage=True):
+    """Anchor target assignment at the reference's configuration (crop 512 x 1760, stride 16, 36 anchors): B images of
+    R = 32 * 110 * 36 = 126 720 rois [B, R, 5] (x1 y1 x2 y2 tracker) with ragged ground truths padded to Mmax / Kmax rows.  Padding
+    rows hold NaN (labels -7) when garbage.  Returns dict(rois, gv [B, Mmax, 4], gi [B, Kmax, 4], g3 [B, Mmax, D3], lb [B, Mmax], Mc,
+    Kc, anchors [36, acols], r3 [B, R, acols] (rois_3d), cen [B, R, 2])."""
+    H, W, A = 32, 110, 36
+    wh = np.stack([rng.uniform(12, 300, A), rng.uniform(12, 200, A)], 1)
+    a2 = np.concatenate([-wh / 2, wh / 2], 1)
+    ys, xs = np.meshgrid(np.arange(H) * 16.0, np.arange(W) * 16.0, indexing="ij")
+    sh = np.stack([xs.ravel(), ys.ravel(), xs.ravel(), ys.ravel()], 1)
+    rois = np.concatenate([(sh[:, None] + a2[None]).reshape(-1, 4), np.tile(np.arange(A), H * W)[:, None]], 1)
+    R = rois.shape[0]
+    anchors = np.zeros((A, acols))
+    anchors[:, :4] = a2
+    anchors[:, 4] = rng.uniform(5, 40, A)
+    anchors[:, 5:8] = rng.uniform(0.5, 4, (A, 3))
+    anchors[:, 8:] = rng.uniform(-2, 2, (A, acols - 8))
+    rb = np.repeat(rois[None], B, 0) + np.concatenate([rng.normal(0, 2, (B, R, 4)), np.zeros((B, R, 1))], 2)
+    rb = rb.astype(dtype)
+    Mc = rng.integers(0, Mmax + 1, B)
+    Mc[0] = Mmax
+    Kc = rng.integers(0, Kmax + 1, B)
+    fill = np.nan if garbage else 0.0
+    gv = np.full((B, Mmax, 4), fill)
+    gi = np.full((B, Kmax, 4), fill)
+    g3 = np.full((B, Mmax, D3), fill)
+    lb = np.full((B, Mmax), -7 if garbage else 1, np.int32)
+    for b in range(B):
+        m = Mc[b]
+        pick = rng.choice(R, m, replace=False)
+        g = rb[b, pick, :4].astype(np.float64) + rng.normal(0, 8, (m, 4))
+        g[:, 2:] = np.maximum(g[:, 2:], g[:, :2] + 4)
+        gv[b, :m] = g
+        lb[b, :m] = rng.integers(1, 4, m)
+        g3[b, :m] = np.concatenate([rng.uniform(0, 1760, (m, 2)), rng.uniform(5, 50, (m, 1)), rng.uniform(0.5, 4, (m, 3)),
+                                    rng.uniform(-3, 3, (m, D3 - 6))], 1)
+        k = Kc[b]
+        gi[b, :k] = rb[b, rng.choice(R, k), :4].astype(np.float64) + rng.normal(0, 20, (k, 4))
+    r3 = np.concatenate([rb[..., :4], anchors[rois[:, 4].astype(np.int64), 4:][None].repeat(B, 0) + rng.normal(0, 0.05, (B, R, acols - 4))],
+                        2).astype(dtype)
+    cen = ((rb[..., :2] + rb[..., 2:4]) / 2).astype(dtype)
+    return dict(rois=rb, gv=gv, gi=gi, g3=g3, lb=lb, Mc=Mc, Kc=Kc, anchors=anchors, r3=r3, cen=cen)

@@ -399,6 +399,34 @@ int gnms_best_targets(const float* pred_params, const float* pred_boxes2d, const
                       int M, const int32_t* pred_counts, const int32_t* gt_counts, float beta, int64_t* best_index, float* best_score,
                       float* targets, void* stream);
 
+/* lib/rpn_util.py:411-524 compute_targets (and lib/core.py:535 iou_ign) for B images: the anchor training targets of the RPN loss
+ * (lib/loss/rpn_3d.py:435-451), on the device.  DESIGN.md 3.10 has the passes and the precision rules.
+ * rois [B][R][ld_rois] x1 y1 x2 y2 (+ the anchor tracker in column tracker_col), float32 or (rois_f64) float64; the arithmetic that
+ * involves a roi alone is done in that type, everything that involves a ground truth in float64, as NumPy's promotion does.
+ * gts_val [B][M][4] with box_lbls [B][M] (>= 1) and gts_ign [B][K][4], float64 x1 y1 x2 y2; image b uses the first val_counts[b] /
+ * ign_counts[b] rows (device int32, NULL = all; clamped to [0, M] / [0, K]); padding rows are never read.  M, K <= GNMS_TARGETS_MAX_GTS
+ * (GNMS_ERR_UNSUPPORTED above).  gts_3d [B][M][D3] float64 with 7 <= D3 <= GNMS_TARGETS_MAX_D3, or D3 = 0: 2D only.  D3 alone sets
+ * the output widths; gts_3d may be NULL when M = 0.
+ * anchor_cols sets decomp_alpha (>= 11) and has_vel (== 12) as anchors.shape[1] does (0: neither); src_3d = rois_3d[:, 4:]
+ * ([B][R][ld_rois_3d], rois_3d_f64) or, with rois_3d NULL, anchors[int64(rois[:, tracker_col]), 4:] (anchors [A][anchor_cols] float64;
+ * a tracker outside [-A, A) gives NaN deltas).  rois_3d_cen [B][R][2] (cen_f64) or NULL: the 3D centre deltas' origin.
+ * means_host / stds_host: NULL or 4 + (decomp ? 9 : 7) float64 (4 with D3 = 0): the call site's normalisation, fused.
+ * Outputs, each optional (NULL), all written on every call (no reliance on zeroed buffers): transforms [B][R][5 + D3 + 2 decomp + vel]
+ * ([B][R][5] with D3 = 0), raw_gt [B][R][5 + D3] ([B][R][5]), float32; ols_max [B][R], ols [B][R][M] (IoU, columns past the
+ * image's count 0), ols_ign [B][R][K] (iou_ign, likewise), float64; best_roi [B][M] int64, the roi each GT keeps (-1: none).
+ * workspace: gnms_compute_targets_workspace_bytes(B, R, M) bytes (8-byte aligned; 12 bytes per GT and image per 256 rois), every
+ * byte of it written before it is read.  Two launches, no atomics, no allocation: graph-capturable. */
+#define GNMS_TARGETS_MAX_GTS 256
+#define GNMS_TARGETS_MAX_D3 24
+size_t gnms_compute_targets_workspace_bytes(int B, int R, int M);
+int gnms_compute_targets(const void* rois, int rois_f64, int B, int R, int64_t ld_rois, const double* gts_val, const int32_t* box_lbls,
+                         int M, const int32_t* val_counts, const double* gts_ign, int K, const int32_t* ign_counts, const double* gts_3d,
+                         int D3, const void* rois_3d, int rois_3d_f64, int64_t ld_rois_3d, const void* rois_3d_cen, int cen_f64,
+                         const double* anchors, int A, int anchor_cols, int tracker_col, double fg_thresh, double ign_thresh,
+                         double bg_thresh_lo, double bg_thresh_hi, double best_thresh, const double* means_host, const double* stds_host,
+                         float* transforms, float* raw_gt, double* ols_max, double* ols, double* ols_ign, int64_t* best_roi,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
