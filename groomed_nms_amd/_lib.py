@@ -108,6 +108,12 @@ _SIGNATURES = {
                                             c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_int64, c_vp,
                                             ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 5
                              + [c_vp] * 8 + [c_vp, ctypes.c_size_t, c_vp]),
+    "gnms_detect3d_scores": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "gnms_detect3d_decode": (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp,
+                                            c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp]),
+    "gnms_detect3d_assemble": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int64, c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp,
+                                              c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -11,6 +11,7 @@
 #include <map>
 #include <mutex>
 #include "nms_kernels.h"
+#include "bbox_decode.h"
 
 namespace {
 
@@ -22,19 +23,7 @@ __global__ __launch_bounds__(256) void bbox_transform_inv_kernel(const float4* _
                                                                  float4* __restrict__ out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    const float4 b = anchors[i % A];
-    float4 d = deltas[i];
-    const float widths = b.z - b.x + 1.0f;                              // :887
-    const float heights = b.w - b.y + 1.0f;                             // :888
-    const float ctr_x = b.x + 0.5f * widths;                            // :889
-    const float ctr_y = b.y + 0.5f * heights;                           // :890
-    if (use_stds) { d.x *= stds.x; d.y *= stds.y; d.z *= stds.z; d.w *= stds.w; }       // :903-907
-    if (use_means) { d.x += means.x; d.y += means.y; d.z += means.z; d.w += means.w; }   // :909-913
-    const float pcx = d.x * widths + ctr_x;                             // :915
-    const float pcy = d.y * heights + ctr_y;                            // :916
-    const float pw = expf(d.z) * widths;                                // :917
-    const float ph = expf(d.w) * heights;                               // :918
-    out[i] = make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw - 1.0f, pcy + 0.5f * ph - 1.0f);   // :924-934
+    out[i] = gnms_bbox_decode(anchors[i % A], deltas[i], means, stds, use_means, use_stds);   // (bbox_decode.h: shared with detect3d.hip)
 }
 
 // One workgroup per image: stable descending sort of the candidates' scores, the first min(K, #candidates) leave.

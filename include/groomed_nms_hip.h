@@ -427,6 +427,42 @@ int gnms_compute_targets(const void* rois, int rois_f64, int B, int R, int64_t l
                          float* transforms, float* raw_gt, double* ols_max, double* ols, double* ols_ign, int64_t* best_roi,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Inference post-processing of the detection head (lib/rpn_util.py:1087-1356, im_detect_3d between `net(im)` and the returned
+ * `aboxes`), around gnms_select_topk and the NMS routes above.  Three stream-ordered launches, no allocation, no workspace:
+ * graph-capturable.  The selection comes BEFORE the decode: only the scores pass touches all A anchors.
+ * ------------------------------------------------------------------------------------------------ */
+/* :1193-1194, :1256.  prob [B][A][C] (column 0 = background, C >= 2), acceptance NULL or [B][A][acceptance_ld] (column 0 is read)
+ * -> scores [B][A] = max(prob[1:]) (* acceptance: one fp32 product, as the reference's), cls_pred [B][A] = argmax(prob[1:]) + 1,
+ * first maximum on ties, a NaN counts as the maximum (np.argmax / np.amax). */
+int gnms_detect3d_scores(const float* prob, const float* acceptance, int64_t acceptance_ld, int B, int A, int C, float* scores,
+                         int32_t* cls_pred, void* stream);
+/* :1111-1170, :1182-1215 for the selected anchors.  sel_index [B][ld_index] (the first K of a row are read; gnms_select_topk's
+ * output), counts [B] or NULL (all K); entries behind an image's count are written as zeros.  bbox_2d [B][A][4], bbox_3d [B][A][D3]
+ * (D3 >= 10 with decomp_alpha: x y z w h l rsin rcos axis head; else >= 7: ... ry), rois [A][5] (x1 y1 x2 y2 tracker), anchors
+ * [n_anchors][anchor_cols] fp32 (columns 4.. = z w h l ry [sin cos]; a tracker outside [0, n_anchors) is clamped), means_host /
+ * stds_host: HOST pointers to norm_cols floats (4 for the 2D box alone, 11 / 13 with the 3D outputs), p2_inv [B][4][4] float64 (needed
+ * for coords_3d_raw only), scale_factor [B] or NULL (1).
+ * Outputs, each optional: boxes2d [B][K][4] = bbox_transform_inv(rois, bbox_2d, means, stds)[sel] / scale_factor, the arithmetic of
+ * gnms_bbox_transform_inv (shared device code) and an fp32 division; coords_3d [B][K][7] = x y (pixels, / scale_factor) z w h l alpha,
+ * fp32 in the reference's operation order, not wrapped; coords_3d_raw [B][K][7] = the camera-space x y z through p2_inv in float64
+ * (from the fp32 products x z and y z), w h l, and rotation_y = alpha + atan2(-z, x) + pi / 2 wrapped into (-pi, pi] in float64
+ * (lib/util.py:641-644), all rounded to fp32. */
+int gnms_detect3d_decode(const int64_t* sel_index, int64_t ld_index, const int32_t* counts, int B, int K, int A, const float* bbox_2d,
+                         const float* bbox_3d, int D3, const float* rois, const float* anchors, int n_anchors, int anchor_cols,
+                         const float* means_host, const float* stds_host, int norm_cols, int decomp_alpha, const double* p2_inv,
+                         const float* scale_factor, float* boxes2d, float* coords_3d, float* coords_3d_raw, void* stream);
+/* :1338-1351.  keep [B][ld_keep]: positions in [0, K) of the kept boxes in output order (int64 when keep_is_i64 -- the layer's `valid`
+ * lists --, int32 otherwise -- gnms_nms_sorted's keep list; NULL: 0, 1, 2, ...), keep_counts [B] (NULL: K).  sel_scores [B][ld_scores]
+ * and sel_index [B][ld_index] from gnms_select_topk, cls_pred [B][A] from gnms_detect3d_scores, boxes2d [B][K][4] and coords_3d
+ * [B][K][7] from gnms_detect3d_decode, rois [A][5].  clip_hw NULL or [B][2] = (height, width) of the original image: x clipped to
+ * [0, width - 1], y to [0, height - 1] (rpn_conf.clip_boxes).  out [B][K][14] = x1 y1 x2 y2 score cls coords_3d[7] tracker, rows
+ * behind the image's count zero; out_counts [B] (optional). */
+int gnms_detect3d_assemble(const void* keep, int keep_is_i64, int64_t ld_keep, const int32_t* keep_counts, const float* sel_scores,
+                           int64_t ld_scores, const int64_t* sel_index, int64_t ld_index, const int32_t* cls_pred, const float* boxes2d,
+                           const float* coords_3d, const float* rois, int B, int K, int A, const float* clip_hw, float* out,
+                           int32_t* out_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
