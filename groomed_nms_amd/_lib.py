@@ -114,6 +114,11 @@ _SIGNATURES = {
                                             c_vp]),
     "gnms_detect3d_assemble": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int64, c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp,
                                               c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "gnms_kitti_eval_plan": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "gnms_kitti_eval_recall": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, c_vp,
+                                              ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gnms_kitti_eval_precision": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, c_vp, ctypes.c_int,
+                                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -463,6 +463,57 @@ int gnms_detect3d_assemble(const void* keep, int keep_is_i64, int64_t ld_keep, c
                            const float* coords_3d, const float* rois, int B, int K, int A, const float* clip_hw, float* out,
                            int32_t* out_counts, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The KITTI object evaluation (data/kitti_split1/devkit/cpp/evaluate_object*.cpp): precision over 41 recall positions for the
+ * image (2D), ground (bird's-eye view) and 3D box of Car / Pedestrian / Cyclist at the three difficulties, and the orientation
+ * similarity (AOS), for V variants (MIN_OVERLAP table + optional ground-truth distance cut) in one pass over the data.
+ * Rows are float64: det [n_det][14] and gt [n_gt_rows][15], columns below; images are ragged through det_offsets / gt_offsets [I + 1]
+ * (int32, ascending from 0); pair_offsets [I + 1] (int64) is the running sum of detections x ground-truth rows per image.
+ * Class / type ids: 0 Car, 1 Pedestrian, 2 Cyclist, 3 Van, 4 Person_sitting, 5 DontCare, 6 anything else (a detection: 0..2, else -1).
+ * A curve is class * 9 + metric * 3 + difficulty (metric 0 image, 1 ground, 2 3D); a task is variant * 27 + curve.
+ * ------------------------------------------------------------------------------------------------ */
+#define GNMS_KITTI_EVAL_MAX_DET 512   /* detections per image: the assigned_detection bit set of a lane */
+#define GNMS_KITTI_EVAL_MAX_GT 1024   /* ground-truth rows per image (DontCare included) */
+#define GNMS_KITTI_EVAL_CURVES 27
+#define GNMS_KITTI_EVAL_PTS 41
+#define GNMS_KITTI_DET_CLASS 0
+#define GNMS_KITTI_DET_ALPHA 1
+#define GNMS_KITTI_DET_X1 2           /* x1 y1 x2 y2 */
+#define GNMS_KITTI_DET_H 6            /* h w l */
+#define GNMS_KITTI_DET_T 9            /* t1 t2 t3 (t2: bottom face) */
+#define GNMS_KITTI_DET_RY 12
+#define GNMS_KITTI_DET_SCORE 13
+#define GNMS_KITTI_GT_TYPE 0
+#define GNMS_KITTI_GT_TRUNC 1
+#define GNMS_KITTI_GT_OCC 2
+#define GNMS_KITTI_GT_ALPHA 3
+#define GNMS_KITTI_GT_X1 4
+#define GNMS_KITTI_GT_H 8
+#define GNMS_KITTI_GT_T 11
+#define GNMS_KITTI_GT_RY 14
+/* Host only, no HIP call: checks the HOST copies of the offsets (ascending from 0, at most GNMS_KITTI_EVAL_MAX_DET detections and
+ * GNMS_KITTI_EVAL_MAX_GT ground-truth rows per image -- nothing is truncated, a larger image is an error) and V, and returns the
+ * number of (detection, ground truth) pairs. */
+int gnms_kitti_eval_plan(const int32_t* det_offsets_host, const int32_t* gt_offsets_host, int I, int V, int64_t* n_pairs);
+/* Everything up to the score lists.  min_overlap [V][3 metrics][3 classes], max_depth [V] (+inf: no cut; else `|| gt.t3 > D` joins
+ * the ground-truth ignore condition), both on the device.  Outputs: overlaps [3][n_pairs] (metric, then pair_offsets[img] + g * nd + j;
+ * criterion -1, on DontCare rows criterion 0), flags [10] ([0] some alpha == -10, [1 + c] eval_image, [4 + c] eval_ground, [7 + c]
+ * eval_3d), tp_scores [V * 27][n_gt_rows] (per ground-truth row the score of its true positive, else -inf; rows of curves that are
+ * off are not written), n_tp and n_gt [V * 27].  The caller sorts each row of tp_scores in descending order. */
+int gnms_kitti_eval_recall(const double* det, const double* gt, const int32_t* det_offsets, const int32_t* gt_offsets,
+                           const int64_t* pair_offsets, int I, int n_det, int n_gt_rows, int64_t n_pairs, const double* min_overlap,
+                           const double* max_depth, int V, double* overlaps, int32_t* flags, double* tp_scores, int32_t* n_tp,
+                           int32_t* n_gt, void* stream);
+/* From the sorted score lists to the curves.  Outputs: thresholds [V * 27][41] and n_thresholds [V * 27] (at most 41), counts
+ * [V * 27][41][3] = tp fp fn summed over the images, precision [V * 27][41] and aos [V][3 classes][3 difficulties][41] after the
+ * max_{i..end} filter, 0 behind n_thresholds and for curves that are off.  similarity [V][9][I][41] is scratch (the per-image
+ * orientation similarity, summed in image order).  A threshold with tp + fp = 0 gives the devkit's 0 / 0 = NaN. */
+int gnms_kitti_eval_precision(const double* det, const double* gt, const int32_t* det_offsets, const int32_t* gt_offsets,
+                              const int64_t* pair_offsets, int I, int n_gt_rows, int64_t n_pairs, const double* min_overlap,
+                              const double* max_depth, int V, const double* overlaps, const int32_t* flags, const double* sorted_scores,
+                              const int32_t* n_tp, const int32_t* n_gt, double* thresholds, int32_t* n_thresholds, int32_t* counts,
+                              double* similarity, double* precision, double* aos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
