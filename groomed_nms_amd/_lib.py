@@ -119,6 +119,9 @@ _SIGNATURES = {
                                               ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "gnms_kitti_eval_precision": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, c_vp, ctypes.c_int,
                                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gnms_kitti_rows_append": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_vp,
+                                              ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "gnms_round6": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -7,6 +7,7 @@
   write_stats                     stats_<cls>_detection.txt ... in saveStats' format (kitti_io.parse_kitti_result reads them)
   run_kitti_eval                  kitti_io.run_kitti_eval_script without the binary
   evaluate_kitti_results_verbose  lib/rpn_util.py:2076-2190: one load, one upload, one evaluate over all 30 variants
+  evaluate_detections             the same dictionaries from a kitti_results.KittiResults (rows collected on the device) instead of a folder
 
 A variant is (min_overlap [3 metrics][3 classes], max_depth or None): the two constants the devkit's sources differ in.  MAIN, SIDE and
 DISTANCE_GRID[(metres, iou)] are the reference's 30.  There is no CPU implementation: the arithmetic runs in the kernels.  Limits:
@@ -28,7 +29,7 @@ from . import _lib
 from .kitti_io import _cfg, parse_kitti_result
 
 __all__ = ["MAIN", "SIDE", "DISTANCE_GRID", "CLASS_NAMES", "TYPE_IDS", "MAX_DET", "MAX_GT", "load_results", "load_labels", "evaluate", "ap",
-           "write_stats", "run_kitti_eval", "evaluate_kitti_results_verbose"]
+           "write_stats", "run_kitti_eval", "evaluate_kitti_results_verbose", "evaluate_detections"]
 
 CLASS_NAMES = ("car", "pedestrian", "cyclist")                       # evaluate_object.cpp:67-70
 TYPE_IDS = {"car": 0, "pedestrian": 1, "cyclist": 2, "van": 3, "person_sitting": 4, "dontcare": 5}
@@ -311,6 +312,18 @@ def run_kitti_eval(results_data, gt_folder, lbls, variant=MAIN, use_40=True, wri
             if path in written:
                 out[key + lbl] = list(parse_kitti_result(path, use_40=use_40))
     return out
+
+
+def evaluate_detections(results, gt_folder, names, lbls, variants=(MAIN,), use_40=True):
+    """run_kitti_eval / evaluate_kitti_results_verbose without the result folder: `results` is a kitti_results.KittiResults holding the
+    split's detections on the device, `names` the label file of every appended image in order (`000001.txt`, ...).  Returns one
+    {'det_2d_car': [easy, mod, hard], 'or_car': ..., ...} per variant (a list in the order of `variants`, or a dict with its keys when
+    `variants` is a dict of name -> variant), built as parse_kitti_result would build them from the stats files."""
+    keys = list(variants) if isinstance(variants, dict) else None
+    vlist = [variants[k] for k in keys] if keys is not None else list(variants)
+    gt, goff = load_labels(gt_folder, list(names))
+    out = [_results_dict(r, lbls, use_40) for r in results.evaluate(gt, goff, variants=vlist)]
+    return dict(zip(keys, out)) if keys is not None else out
 
 
 def _report(results, lbls, test_iter, use_logging):

@@ -514,6 +514,39 @@ int gnms_kitti_eval_precision(const double* det, const double* gt, const int32_t
                               const int32_t* n_tp, const int32_t* n_gt, double* thresholds, int32_t* n_thresholds, int32_t* counts,
                               double* similarity, double* precision, double* aos, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Detections -> the detection rows above, as the devkit would parse them from the reference's result files (lib/train_test.py:102-109,
+ * lib/rpn_util.py:1489-1631), appended on the device (csrc/kitti_rows.hip).
+ * det [B][Kmax][det_cols = 14] fp32 (x1 y1 x2 y2 score cls u v depth w h l alpha tracker) and counts [B] from gnms_detect3d_assemble,
+ * p2_inv [B][4][4] float64.  Per image the first min(nms_topN_post, counts[b]) rows take part; a row is kept when (double)score >
+ * score_thres; kept rows keep their order.  Float64 from there: (x, y, z) = rows 0-2 of p2_inv (u depth, v depth, depth, 1), y += h / 2,
+ * ry = snap_to_pi(alpha + atan2(-z, x) + pi / 2), alpha = snap_to_pi(ry - atan2(-z, x) - pi / 2); each of the 13 numeric fields v becomes
+ * the double that its '%.6f' text parses to (exact for finite |v| < 1e9; other values are stored as they are and counted).
+ * class_ids [n_lbls] (1 <= n_lbls <= GNMS_KITTI_ROWS_MAX_LBLS): the row's class id for label index (int)cls - 1; an index outside the
+ * table writes class -1 and sets GNMS_KITTI_ROWS_ERR_CLASS.  kept_scratch [B] int32 is scratch.
+ * rows [capacity][14] float64 and lbl_index [capacity] int32 (optional: the label index of each row) are appended to behind
+ * state[END] rows; offsets [n_offsets] int32 receives the running end at [image_base + b + 1] (the caller keeps offsets[0] = 0).  A row
+ * at or beyond `capacity` and an offsets entry at or beyond n_offsets are not stored; state[END] / state[IMAGES] still count them, so
+ * the caller sees what was needed.  state [GNMS_KITTI_ROWS_STATE_WORDS] int64, zeroed by the caller before the first call, lives on
+ * the device: consecutive calls on one stream append without the host reading anything.  Three stream-ordered launches; no workgroup
+ * waits for another. */
+#define GNMS_KITTI_ROWS_MAX_LBLS 16
+#define GNMS_KITTI_ROWS_STATE_WORDS 8
+#define GNMS_KITTI_ROWS_STATE_END 0      /* rows appended so far (needed, not clipped to capacity) */
+#define GNMS_KITTI_ROWS_STATE_IMAGES 1   /* images appended so far (needed, not clipped to n_offsets - 1) */
+#define GNMS_KITTI_ROWS_STATE_OUTSIDE 2  /* fields that are not finite or not below 1e9 in magnitude */
+#define GNMS_KITTI_ROWS_STATE_ERRORS 3   /* GNMS_KITTI_ROWS_ERR_* */
+#define GNMS_KITTI_ROWS_STATE_PENDING 4  /* the running end between the write and the commit launch */
+#define GNMS_KITTI_ROWS_ERR_CLASS 1      /* a label index outside class_ids */
+#define GNMS_KITTI_ROWS_ERR_ANGLE 2      /* an angle so large that 1024 steps of 2 pi did not bring it into (-pi, pi] */
+int gnms_kitti_rows_append(const float* det, int det_cols, const int32_t* counts, const double* p2_inv, int B, int Kmax,
+                           int nms_topN_post, double score_thres, const int32_t* class_ids, int n_lbls, int32_t* kept_scratch,
+                           double* rows, int32_t* lbl_index, int64_t capacity, int32_t* offsets, int n_offsets, int image_base,
+                           int64_t* state, void* stream);
+/* out[i] = the double that the '%.6f' text of in[i] parses to (in != out); outside_count (optional, device) is incremented for every
+ * element that is not finite or not below 1e9 in magnitude (copied as it is). */
+int gnms_round6(const double* in, double* out, int64_t n, int64_t* outside_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
