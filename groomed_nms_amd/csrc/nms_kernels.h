@@ -978,6 +978,14 @@ __device__ __forceinline__ void bitmask_boxes_body(const float* __restrict__ box
     // through the CU for ~3 us of arithmetic: 48 MB of L2 -> CU traffic in the first microseconds, the late waves' loads 6-8 us behind, and
     // the CU's second workgroup (younger waves) finishing 7-8 us after the first (profiles/r06j_bits_timeline.txt: image 0 done at 15 us,
     // image 7 at 23).  256 workgroups of two blocks pull half the bytes and have their CU to themselves.
+    // LATE (round 7; the two-block route): the dependent gather rankof[xidx[p]] -- 64 distinct lines per instruction, the slow one -- is off the
+    // path to the rows.  A wave requests its row boxes, column boxes and the columns' x-order indices, computes the hull when the boxes are
+    // there, issues the gather BEHIND the hull (every wave's box loads are then in front of it in the texture pipe's queue) and waits for it only
+    // where the first finished word is parked, one rows loop later: a column's rank says nothing but WHICH word of the LDS row that is.  The
+    // four ranks stay in registers (one workgroup per CU: 128 VGPRs); the stash and its 16 KiB of LDS are gone here.  24.0 -> 22.2 us.
+    // (KBW = 1 stays as it was: at its 64 VGPRs the same order spills 11 registers where the stash version spills 3.  Measured and not kept,
+    // LABNOTES R7: the LDS rows zeroed behind the issue of the loads; the row write-out from column 64 kb on.)
+    constexpr bool LATE = ROWBUF && !CHUNKLOOP && KBW > 1;
     if (ROWBUF) {
         const int kbr = bx * KBW;                             // KBW rank blocks per workgroup, wave w = column chunk w
         if (kbr * 64 >= n) return;
@@ -993,13 +1001,30 @@ __device__ __forceinline__ void bitmask_boxes_body(const float* __restrict__ box
     const int c0 = chunk * kCols;
     const bool idle = (kbg * KBW >= L.NB || kbg * KBW * 64 >= n || c0 >= n || chunk >= nchunk);   // (ragged images)
     if (!ROWBUF && idle) return;
-    if (!idle) {                                                     // (a chunk LOOP here cost 25 % in code quality at N = 4096: 24.5 -> 31 us)
-    // the row boxes of the first rank block are requested before the column side is worked on
-    float4 rb_next = I.rbox[min(kbg * KBW * 64 + lane, n - 1)];     // (rank order, written by the score sort: no order -> box gather)
+    float4 rb_next;
     float4 cb[CPL];
     float carea[CPL];
     int crank[CPL];
     bool cok = true;
+    if (LATE) {
+        // (no branch around the requests: a wave without columns -- ragged images -- reads clamped duplicates like the lanes past the last
+        // column; under `if (!idle)` the values are merged with the idle path's behind the loads, which waits for every one of them here)
+        rb_next = I.rbox[min(kbg * KBW * 64 + lane, n - 1)];
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) cb[j] = I.xbox[min(c0 + 64 * j + lane, n - 1)];
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) crank[j] = I.xidx[min(c0 + 64 * j + lane, n - 1)];   // (the x-order index; its rank below)
+    }
+    if (!idle) {                                                     // (a chunk LOOP here cost 25 % in code quality at N = 4096: 24.5 -> 31 us)
+    if (LATE) {
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            carea[j] = (cb[j].z - cb[j].x) * (cb[j].w - cb[j].y);
+            cok &= (carea[j] > 0.0f) && (carea[j] < INFINITY);
+        }
+    } else {
+    // the row boxes of the first rank block are requested before the column side is worked on
+    rb_next = I.rbox[min(kbg * KBW * 64 + lane, n - 1)];            // (rank order, written by the score sort: no order -> box gather)
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
         // (round 6: column 64 j + lane, not CPL lane + j.  With four CONSECUTIVE columns per lane the lanes of one load instruction sat 64 bytes
@@ -1013,14 +1038,16 @@ __device__ __forceinline__ void bitmask_boxes_body(const float* __restrict__ box
         carea[j] = (cb[j].z - cb[j].x) * (cb[j].w - cb[j].y);
         cok &= (carea[j] > 0.0f) && (carea[j] < INFINITY);
     }
+    }
     // Decision !(fl(inter/uni) <= thr) WITHOUT the division.  With d = fma(-thr, uni, inter) (one rounding, sign exact):
     //   inter/uni - thr = d/uni,  so  |d| > guard*uni  puts the exact quotient more than `guard` (8 ulp of the threshold)
     // away from thr, hence its fp32 rounding on the same side, and the pair is decided by the sign of d.  That needs
     // uni > 0 and finite, which holds whenever both boxes have a positive finite area (inter <= min(area) in fp32 as in
     // exact arithmetic because subtraction/multiplication round monotonically, so uni >= max(area) > 0): checked once per
     // column box and per row.  Rows/columns that fail, and the pairs inside the guard band, take the exact IEEE division.
-    // (two workgroups per CU leave 64 VGPRs: the columns' ranks, not needed before the words are parked, wait in LDS meanwhile)
-    constexpr bool STASH = ROWBUF && !CHUNKLOOP && CPL == 4;
+    // (KBW = 1: two workgroups per CU leave 64 VGPRs: the columns' ranks, not needed before the words are parked, wait in LDS meanwhile.
+    // KBW = 2 is one workgroup per CU with 128 VGPRs: the four ranks stay in registers, their gather in flight behind the first rows loop)
+    constexpr bool STASH = ROWBUF && !CHUNKLOOP && CPL == 4 && KBW == 1;
     int* const crank_lds = reinterpret_cast<int*>(smem + (size_t)KBW * L.NC * 8) + threadIdx.x;   // [CPL][1024] (behind the KBW rows)
     if (STASH) {
 #pragma unroll
@@ -1035,6 +1062,13 @@ __device__ __forceinline__ void bitmask_boxes_body(const float* __restrict__ box
     for (int j = 1; j < CPL; ++j) { hx0 = fminf(hx0, cb[j].x); hx1 = fmaxf(hx1, cb[j].z); hy0 = fminf(hy0, cb[j].y); hy1 = fmaxf(hy1, cb[j].w); }
     hx0 = wave_min_f(hx0); hy0 = wave_min_f(hy0); hx1 = wave_max_f(hx1); hy1 = wave_max_f(hy1);
     const bool cull = cols_ok && (thr >= 0.0f);
+    if (LATE) {
+        // the gather goes out BEHIND the hull (the sixteen waves' box loads are all in front of it in the texture pipe's queue) and is in flight
+        // during the first rows loop; clamped duplicates included: they are not parked, see `live` below
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) crank[j] = I.rankof[crank[j]];
+    }
     GNMS_BT();
 #pragma unroll 1
     for (int kw = 0; kw < KBW; ++kw) {
@@ -1169,7 +1203,8 @@ __device__ __forceinline__ void bitmask_boxes_body(const float* __restrict__ box
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
             const int cr = STASH ? crank_lds[j * 1024] : crank[j];
-            if (cr != 0x7fffffff) Wk[cr] = ((u64)wd[1][j] << 32) | wd[0][j];
+            const bool live = LATE ? (c0 + 64 * j + lane < n) : (cr != 0x7fffffff);
+            if (live) Wk[cr] = ((u64)wd[1][j] << 32) | wd[0][j];
         }
     }
     }   // !idle
