@@ -441,8 +441,10 @@ __global__ __launch_bounds__(1024) void sort_scores_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
-// K1 for N > 1024: the same two sorts (scores descending; boxes by x centre) spread over R = P/1024 workgroups per image.
-//   sort_runs_kernel   every workgroup sorts one run of 1024 keys in LDS (block_sort<1>) and parks it in global scratch
+// K1 as runs + merge: the same two sorts (scores descending; boxes by x centre) spread over R = P/1024 workgroups per image.  The route of
+// N > 4096; up to 2048 keys the counting sort further down took over in round 5, and 2048 < N <= 4096 the ranked runs behind these two in
+// round 8 (launch_sorts in nms_layer.hip has the table; GNMS_RANK_SORT=0 brings that range back here).
+//   sort_runs_kernel  every workgroup sorts one run of 1024 keys in LDS (block_sort<1>) and parks it in global scratch
 //                      (the bit-matrix region W: nothing lives there before K2);
 //   sort_merge_kernel  every workgroup loads ALL runs of its image into LDS and ranks its own 1024 keys: final position =
 //                      own position + sum over the other runs of (number of keys below mine), R-1 branch-free binary searches
@@ -456,7 +458,7 @@ __device__ __forceinline__ u64 sort_key_of(int role, const float* __restrict__ s
     return column_key(reinterpret_cast<const float4*>(boxes_img)[i], i, nbands, zlo, zscale);
 }
 
-// (run r of image b, role) -- also called from the launch that carries a slice of the matrix write (nms_layer.hip)
+// (run r of image b, role)
 __device__ __forceinline__ void sort_runs_body(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
                                                const int* __restrict__ counts, char* ws, gnms_ws_layout L, int P, const int r, const int b,
                                                const int role, const int mode3d = 0) {
@@ -543,6 +545,184 @@ __global__ __launch_bounds__(1024) void sort_merge_kernel(const float* __restric
                                                           const int* __restrict__ counts, char* ws, gnms_ws_layout L,
                                                           long long* __restrict__ order_out, int mode3d) {
     sort_merge_body<R>(scores, boxes, N, counts, ws, L, order_out, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, mode3d);
+}
+
+// ------------------------------------------------------------------------------------------------
+// K1 for 2048 < N <= 4096 (round 8): runs AND ranks in ONE launch, no workgroup waiting for another.  Runs + merge cost 8.1 + 6.4 us and a
+// launch boundary at B = 8 on 64 workgroups each, the keys going through HBM scratch in between.  Here workgroup (r, image, role) of
+// 16 builds ALL 4096 keys of its image and role (thread t: keys 4t .. 4t+3), each of its 16 waves sorts its own 256 keys in registers
+// (phase 1 of block_sort<4>: no barrier inside), the 16 sorted runs go into LDS, and the workgroup ranks the 256 keys of run r against all
+// runs: thread (key, quarter) searches the four runs of its quarter in lock step, the four partial counts meet in LDS.  Every image's
+// run sort is repeated 16 times -- on CUs that stood idle -- and that is what removes the second launch, the scratch and every hand-off.
+// 16 * B * roles workgroups: 256 at B = 8 with boxes; taken while that is one round of the machine (launch_sorts).  The flags are decided by workgroup 0 of each role alone, on the keys it holds
+// (as sort_count_body does): no flag depends on an earlier launch.
+// ------------------------------------------------------------------------------------------------
+constexpr int kRankRuns = 16;            // waves per workgroup = runs per image = workgroups per image and role
+constexpr int kRankRunKeys = 256;        // keys per run (E = 4 per lane)
+
+// lane ^ m of a 32-bit value, m a compile-time constant after unrolling: DPP where one exists (quad_perm for 1 and 2, row_ror:8 for 8, the two
+// halves of 4 as row_ror:12 into banks 0, 2 and row_ror:4 into banks 1, 3), ds_bpermute for 16 and 32.  18 of the run sort's 21 shuffle stages
+// are DPP that way; with ds_bpermute for all of them the launch took 14.6 us instead of 11.5 at B = 8 (LABNOTES R8.2)
+__device__ __forceinline__ unsigned xor_lanes32(unsigned v, int m) {
+    switch (m) {
+        case 1: return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);    // quad_perm:[1,0,3,2]
+        case 2: return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);    // quad_perm:[2,3,0,1]
+        case 4: {
+            const int a = __builtin_amdgcn_update_dpp(0, (int)v, 0x12C, 0xF, 0x5, false);         // row_ror:12 = lane + 4 -> lanes with bit 2 clear
+            return (unsigned)__builtin_amdgcn_update_dpp(a, (int)v, 0x124, 0xF, 0xA, false);      // row_ror:4  = lane - 4 -> lanes with bit 2 set
+        }
+        case 8: return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true);   // row_ror:8
+        default: break;
+    }
+    return __shfl_xor(v, m, 64);
+}
+__device__ __forceinline__ u64 xor_lanes(u64 v, int m) {
+    return ((u64)xor_lanes32((unsigned)(v >> 32), m) << 32) | xor_lanes32((unsigned)(v & 0xffffffffu), m);
+}
+
+// every wave sorts the 256 keys of its lanes' r[0..3] ascending (lane l ends with positions 4l .. 4l+3 of the run): the network of
+// block_sort's phase 1 for E = 4, fully unrolled so that every shuffle distance is a constant
+__device__ __forceinline__ void wave_sort_256(u64 (&r)[4]) {
+    const int i0 = ((int)threadIdx.x & 63) * 4;
+#pragma unroll
+    for (int k = 2; k <= kRankRunKeys; k <<= 1) {
+        const int kd = (k == kRankRunKeys) ? 0 : k;
+#pragma unroll
+        for (int j = k >> 1; j >= 4; j >>= 1) {
+            const bool keepmin = ((i0 & kd) == 0) == ((i0 & j) == 0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const u64 o = xor_lanes(r[e], j / 4);
+                r[e] = ((o < r[e]) == keepmin) ? o : r[e];
+            }
+        }
+#pragma unroll
+        for (int jj = 2; jj >= 1; jj >>= 1) {
+            if (jj < k) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if ((e & jj) == 0) {
+                        const bool up = ((i0 + e) & kd) == 0;
+                        const u64 a = r[e], b = r[e | jj];
+                        if ((a > b) == up) { r[e] = b; r[e | jj] = a; }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// (workgroup r of 16 of image b, role): grid (16, B, roles), 1024 threads, 4096 * 8 bytes of dynamic LDS; 2048 < N <= 4096
+__device__ __forceinline__ void sort_ranked_runs_body(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
+                                                      const int* __restrict__ counts, char* ws, gnms_ws_layout L,
+                                                      long long* __restrict__ order_out, const int r, const int b, const int role,
+                                                      const int mode3d = 0) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    u64* keys = reinterpret_cast<u64*>(smem);                          // [16][256]: the image as 16 sorted runs (padding ~0: behind everything)
+    __shared__ int part[3][kRankRunKeys];                              // partial counts of quarters 1 .. 3
+    const int n = gnms_count(counts, b, N);
+    ImgPtrs I = img_ptrs(ws, L, b);
+    const int t = threadIdx.x;
+    const float* s = scores + (size_t)b * N;
+    const float4* bx = boxes ? reinterpret_cast<const float4*>(boxes) + (size_t)b * N : nullptr;
+    float zlo = 0.0f, zscale = 0.0f;
+    if (role == 1 && mode3d > 1) block_z_bands(bx, n, mode3d, &zlo, &zscale);
+    u64 k[4];
+    int flag = 1;                                                      // workgroup 0: role 0 "the scores came in sorted", role 1 "every box is plain"
+    if (role == 0) {
+        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (4 * t + 3 < N && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+            const float4 q = reinterpret_cast<const float4*>(s)[t];
+            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (4 * t + e < n) v[e] = s[4 * t + e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) k[e] = (4 * t + e < n) ? (((u64)gnms_desc_key(v[e]) << 32) | (unsigned)(4 * t + e)) : ~0ull;   // (sort_key_of)
+        if (r == 0) {                                                  // ascending keys in index order = the scores came in sorted
+            const u64 next = (4 * t + 4 < n) ? sort_key_of(0, s, nullptr, 4 * t + 4, 0, 0.0f, 0.0f) : ~0ull;
+            flag = (4 * t + 1 >= n || k[0] < k[1]) && (4 * t + 2 >= n || k[1] < k[2]) && (4 * t + 3 >= n || k[2] < k[3]) && (4 * t + 4 >= n || k[3] < next);
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = 4 * t + e;
+            k[e] = ~0ull;
+            if (i < n) {
+                const float4 v = bx[i];
+                k[e] = column_key(v, i, mode3d, zlo, zscale);
+                flag &= box_orders_plainly(v) ? 1 : 0;                 // (tested on the box the key is made of, as sort_count_body does)
+            }
+        }
+    }
+    wave_sort_256(k);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) keys[4 * t + e] = k[e];
+    // what only one workgroup per image and role does: the flags (it holds every key, so it decides alone), the counters, the call counter,
+    // the hand-off granules
+    if (r == 0) {
+        const int all = __syncthreads_and(flag);                       // (also: the runs are in LDS)
+        if (role == 0) {
+            if (t < 8 && !(boxes && t == 6)) I.misc[t] = (t == 2) ? all : 0;               // ([6]: the x sort's)
+            if (t == 8) I.misc[8] = gnms_next_epoch(I.misc[8]);
+            for (int i = t; i < 17 * 32; i += 1024) I.gran[i] = 0ull;
+        } else if (t == 0) {
+            I.misc[6] = all ? 0 : 1;
+        }
+    } else {
+        __syncthreads();
+    }
+    const int key = t & (kRankRunKeys - 1), quarter = t >> 8;
+    const u64 mine = keys[r * kRankRunKeys + key];
+    const bool live = mine != ~0ull;
+    const int idx = (int)((unsigned)mine & (role == 0 ? 0xffffffffu : kColIdxMask));
+    // what leaves with the key -- its score, its box -- is fetched by INPUT index, known before the searches: requested here (sort_merge_body)
+    float sv = 0.0f;
+    float4 bv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (quarter == 0 && live) {
+        if (role == 0) sv = s[idx];
+        if (bx) bv = bx[idx];
+    }
+    int cnt = 0;
+    if (live) {
+        const u64* q4 = keys + quarter * 4 * kRankRunKeys;             // the four runs of this quarter
+        int pos[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int h = kRankRunKeys / 2; h >= 1; h >>= 1) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pos[j] += (q4[j * kRankRunKeys + pos[j] + h - 1] < mine) ? h : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cnt += (quarter * 4 + j == r) ? key : pos[j] + ((q4[j * kRankRunKeys + pos[j]] < mine) ? 1 : 0);
+        if (quarter) part[quarter - 1][key] = cnt;
+    }
+    __syncthreads();
+    if (quarter == 0 && live) {
+        const int rank = cnt + part[0][key] + part[1][key] + part[2][key];
+        if (role == 0) {
+            I.order[rank] = idx;
+            I.rankof[idx] = rank;
+            I.sscore[rank] = sv;
+            if (bx) I.rbox[rank] = bv;                                 // (the from-boxes layer: row boxes of the bit matrix)
+            if (order_out) order_out[(size_t)b * N + rank] = idx;
+        } else {
+            column_store(I, rank, idx, bv, mode3d);
+        }
+    }
+    if (role == 0) {
+        const int kp = n + r * 1024 + t;                               // padding ranks map to themselves (order is a permutation of [0, N))
+        if (kp < N) {
+            I.order[kp] = kp; I.rankof[kp] = kp; I.sscore[kp] = 0.0f;
+            if (order_out) order_out[(size_t)b * N + kp] = kp;
+        }
+    }
+}
+
+__global__ __launch_bounds__(1024) void sort_ranked_runs_kernel(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
+                                                                const int* __restrict__ counts, char* ws, gnms_ws_layout L,
+                                                                long long* __restrict__ order_out, int mode3d) {
+    sort_ranked_runs_body(scores, boxes, N, counts, ws, L, order_out, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, mode3d);
 }
 
 

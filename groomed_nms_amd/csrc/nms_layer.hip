@@ -1003,24 +1003,51 @@ int launch_bitmask_boxes(const float* boxes, int B, int N, const int32_t* counts
     return GNMS_OK;
 }
 
-// K1: stable descending score sort (+ the x-centre sort of the boxes when `boxes` is given).  One workgroup per image up to
-// 1024 keys, the cooperative two-kernel sort above that.
+// GNMS_RANK_SORT=0: 2048 < N <= 4096 sorts as runs + merge, two launches (developer / test switch, read once: the pair stays reachable for
+// A/B runs and the tests)
+bool rank_sort_enabled() {
+    static const bool on = [] { const char* e = getenv("GNMS_RANK_SORT"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
+// K1: stable descending score sort (+ the x-centre sort of the boxes when `boxes` is given).  Which kernels (measured per call in a replayed
+// graph of 20, MI355X, LABNOTES R8.1; W = workgroups of the ranked-runs launch = 16 * B * roles):
+//   N <= 2048; N <= 4096 with N / 64 * B * roles <= CUs (B <= 2 with boxes)   by counting, one launch (sort_count_kernel)
+//   2048 < N <= 4096 otherwise, while W <= CUs (B <= 8 with boxes, 16 without)  16 wave-sorted runs per workgroup, ranked in the same launch
+//                                                                               (sort_ranked_runs_kernel, round 8)
+//   everything else (N > 4096; W > CUs; GNMS_RANK_SORT=0)                       runs of 1024 + rank merge, two launches
 // mode3d: 0 = `boxes` are 2D boxes (columns by x centre); >= 1 = pseudo boxes of cuboids whose records lie in the workspace (columns by
 // (z band, x centre) with that many bands; the sort also leaves the records in column order, ImgPtrs::xrec)
+// route (gnms_profile_sorts): 0 = the table above, 1 = runs + merge, 2 = ranked runs
 int launch_sorts(const float* scores, const float* boxes, int B, int N, const int32_t* counts, char* ws, const gnms_ws_layout& L, int P2,
-                 int64_t* order, hipStream_t st, int mode3d = 0) {
+                 int64_t* order, hipStream_t st, int mode3d = 0, int route = 0) {
     int rc;
     const int roles = boxes ? 2 : 1;
     // up to 2048 keys: by counting, N / 64 workgroups per image and role (sort_count_kernel)
     constexpr bool count_sort = true;
-    // (... and up to 4096 keys where its N / 64 workgroups per image and role are ONE round of the machine -- B <= 2: 256 compares per thread,
-    // ~8 us in one launch against 14 us of runs + merge; from two rounds on the merge sort wins, LABNOTES R5.6)
-    if (count_sort && (N <= 2048 || (N <= 4096 && (long)B * ((N + 63) / 64) * roles <= (long)device_cu_count()))) {
+    // (... and up to 4096 keys where its N / 64 workgroups per image and role are ONE round of the machine -- B <= 2 with boxes: 256 compares
+    // per thread.  N = 4096 with boxes, us per call: B = 1 counting 7.3, ranked runs 9.7, runs + merge 12.4; B = 2 10.05 / 9.9 / 12.6 -- level
+    // with the ranked runs, so the counting sort keeps it; from two rounds on it loses, LABNOTES R5.6)
+    if (route == 0 && count_sort && (N <= 2048 || (N <= 4096 && (long)B * ((N + 63) / 64) * roles <= (long)device_cu_count()))) {
         const int NP = (N + 63) & ~63;
         if (NP % 128 == 0 && (long)B * (NP / 32) * roles <= (long)device_cu_count())   // half the compares per thread while the grid is one round
             sort_count_kernel<32><<<dim3(NP / 32, B, roles), 1024, (size_t)NP * 8, st>>>(scores, boxes, N, counts, ws, L, (long long*)order, mode3d);
         else
             sort_count_kernel<64><<<dim3(NP / 64, B, roles), 1024, (size_t)NP * 8, st>>>(scores, boxes, N, counts, ws, L, (long long*)order, mode3d);
+        GNMS_CHECK_LAUNCH();
+        return GNMS_OK;
+    }
+    // 2048 < N <= 4096 past that: the runs and their ranks in one launch, 16 workgroups per image and role -- while those are one round of the
+    // machine.  N = 4096, us per call, ranked runs / runs + merge: with boxes B = 4 10.3 / 12.8, B = 8 11.5 / 13.5, B = 16 (512 workgroups)
+    // 16.4 / 15.0; scores alone B = 8 9.5 / 12.4, B = 16 10.3 / 12.7, B = 32 (512 workgroups) 15.4 / 13.9; N = 2112 and 3072 at B = 8 with boxes
+    // 10.1 / 12.7 and 10.5 / 13.2.  Every workgroup repeats its image's run sort, so a second round costs more than the second launch saves.
+    if (route == 2 || (route == 0 && P2 == 4096 && rank_sort_enabled() && (long)kRankRuns * B * roles <= (long)device_cu_count())) {
+        if (P2 != 4096) {
+            gnms_set_error("launch_sorts: the ranked-runs sort takes 2048 < N <= 4096 (N=%d)", N);
+            return GNMS_ERR_UNSUPPORTED;
+        }
+        sort_ranked_runs_kernel<<<dim3(kRankRuns, B, roles), 1024, (size_t)kRankRuns * kRankRunKeys * 8, st>>>(scores, boxes, N, counts, ws, L,
+                                                                                                             (long long*)order, mode3d);
         GNMS_CHECK_LAUNCH();
         return GNMS_OK;
     }
@@ -1829,6 +1856,51 @@ extern "C" int gnms_profile_bitmask_boxes(const float* boxes, int B, int N, cons
     if (B == 0 || N == 0) return GNMS_OK;
     const gnms_ws_layout L = gnms_make_layout(N);
     return launch_bitmask_boxes(boxes, B, N, counts, nms_threshold, (char*)workspace, L, (hipStream_t)stream);
+}
+
+// Profiling / test hook: ONLY the sorts (K1) of the 2D layer, on a chosen route, and what they leave in the workspace copied out.
+namespace {
+__global__ void export_sorts_kernel(int N, const int* __restrict__ counts, char* ws, gnms_ws_layout L, int has_boxes, int* __restrict__ order,
+                                    int* __restrict__ rankof, float* __restrict__ sscore, float4* __restrict__ rbox, int* __restrict__ xidx,
+                                    float4* __restrict__ xbox, int* __restrict__ flags) {
+    using namespace gnms;
+    const int b = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = gnms_count(counts, b, N);
+    ImgPtrs I = img_ptrs(ws, L, b);
+    if (k == 0 && flags) { flags[2 * b] = I.misc[2]; flags[2 * b + 1] = has_boxes ? I.misc[6] : 0; }
+    if (k >= N) return;
+    const size_t o = (size_t)b * N + k;
+    if (order) order[o] = I.order[k];
+    if (rankof) rankof[o] = I.rankof[k];
+    if (sscore) sscore[o] = I.sscore[k];
+    // (the sorts write these for the image's n boxes only: zeros behind them)
+    const bool live = has_boxes && k < n;
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (rbox) rbox[o] = live ? I.rbox[k] : zero;
+    if (xidx) xidx[o] = live ? I.xidx[k] : 0;
+    if (xbox) xbox[o] = live ? I.xbox[k] : zero;
+}
+}  // namespace
+
+extern "C" int gnms_profile_sorts(const float* scores, const float* boxes, int B, int N, const int32_t* counts, int route, int32_t* order,
+                                  int32_t* rankof, float* sscore, float* rbox, int32_t* xidx, float* xbox, int32_t* flags, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    gnms_params P;
+    gnms_default_params(&P);
+    int rc = check_common("gnms_profile_sorts", B, N, N, &P, workspace, workspace_bytes);
+    if (rc) return rc;
+    GNMS_CHECK_ARG(route >= 0 && route <= 2, "gnms_profile_sorts: route %d (0 default, 1 runs + merge, 2 ranked runs)", route);
+    if (B == 0 || N == 0) return GNMS_OK;
+    GNMS_CHECK_ARG(scores != nullptr, "gnms_profile_sorts: scores is NULL");
+    const gnms_ws_layout L = gnms_make_layout(N);
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = launch_sorts(scores, boxes, B, N, counts, (char*)workspace, L, next_pow2(N), nullptr, st, 0, route))) return rc;
+    if (order || rankof || sscore || rbox || xidx || xbox || flags) {
+        export_sorts_kernel<<<dim3(gnms_div_up(N, 256), B), 256, 0, st>>>(N, counts, (char*)workspace, L, boxes ? 1 : 0, order, rankof, sscore,
+                                                                          (float4*)rbox, xidx, (float4*)xbox, flags);
+        GNMS_CHECK_LAUNCH();
+    }
+    return GNMS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -244,6 +244,15 @@ int gnms_profile_bitmask(const float* iou, int B, int N, int64_t ld, const int32
 int gnms_profile_bitmask_boxes(const float* boxes, int B, int N, const int32_t* counts, float nms_threshold, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* profiling / test hook: only the sorts in front of the 2D layer (scores descending; with `boxes` [B][N][4], which may be NULL, also the
+ * boxes by x centre), on a chosen route: 0 = what the layer takes, 1 = runs + merge (two launches), 2 = ranked runs (one launch,
+ * 2048 < N <= 4096, GNMS_ERR_UNSUPPORTED elsewhere).  What the sorts leave in the workspace is copied into the caller's arrays, each
+ * [B][N] (rbox, xbox: [B][N][4]) and each optional: order, rankof, sscore, and with boxes rbox, xidx, xbox (zeros behind an image's
+ * count); flags [B][2] = "the scores came in sorted", "some box is not plain". */
+int gnms_profile_sorts(const float* scores, const float* boxes, int B, int N, const int32_t* counts, int route, int32_t* order,
+                       int32_t* rankof, float* sscore, float* rbox, int32_t* xidx, float* xbox, int32_t* flags, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* Per-launch timing of the two HBM-bound launches inside whatever call sequence the caller runs (bench.py's roofline line).
  * gnms_profile_events(1) arms it: from then on every launch that writes an N x N overlap matrix (slot GNMS_PROF_MATRIX_WRITE:
  * gnms_iou2d, gnms_iou3d_*, gnms_forward_with_iou2d / _iou3d), every launch of the kernel that reads one (slot GNMS_PROF_MATRIX_READ:
