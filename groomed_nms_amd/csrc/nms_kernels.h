@@ -880,9 +880,26 @@ __device__ __forceinline__ float4 load_nt_f4(const float* p) {
     return v;
 }
 
+// Rows of W out of an LDS row buffer, WRITE-THROUGH (round 9): `words` words (a row of NC, or KBW adjacent rows: they are adjacent in W as
+// in LDS) from `src` to `dst`, every lane 16 bytes per pass -- ds_read_b128, one 16-byte buffer store with sc1 (aux = 16).  A plain store
+// leaves its line dirty in the XCD's L2, and the end-of-kernel release writes all of them back while the next launch waits: 16.8 MB of W at
+// B = 8, N = 4096, 1.5 us at the end of this kernel and 0.8 at the start of tail_write_kernel (LABNOTES R9.1).  An sc1 store leaves as it is issued, while other workgroups still
+// compute.  (8-byte sc1 stores cost 2.7x the time per byte: the pairs matter.)  Needs words % 2 == 0 and 16-byte aligned src / dst:
+// NC = round_up(N, 4), the rows of W start 32-byte aligned, the row buffer is the 16-byte aligned base of the LDS.  Every consumer of W runs
+// in a later launch.  The descriptor covers exactly the bytes of this copy: an offset past them would be dropped by the hardware.
+typedef unsigned int gnms_u4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void w_rows_write_through(u64* dst, const u64* src, int words) {
+    const unsigned bytes = (unsigned)words * 8u;
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(dst, 0, (int)bytes, 0x00020000);   // raw buffer, 32-bit data format
+    for (unsigned o = threadIdx.x * 16u; o < bytes; o += blockDim.x * 16u)
+        __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const gnms_u4*>(reinterpret_cast<const char*>(src) + o), rsrc, (int)o, 0, 16);
+}
+// which kernels write W through (launch_bitmask_boxes / launch_bitmask in nms_layer.hip pass it on; w_write_through_routes there)
+enum : int { kWtKbw2 = 1, kWtKbw1 = 2, kWtChunkLoop = 4, kWtMatrixIn = 8 };
+
 template <bool VEC, int WAVES = kMaskWaves, int RB = kMaskRB>
 __global__ __launch_bounds__(WAVES * 64) void bitmask_kernel(const float* __restrict__ iou, int N, long ld, const int* __restrict__ counts,
-                                                                  float thr, char* ws, gnms_ws_layout L, int full) {
+                                                                  float thr, char* ws, gnms_ws_layout L, int full, int wt) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int b = blockIdx.z;
@@ -895,7 +912,7 @@ __global__ __launch_bounds__(WAVES * 64) void bitmask_kernel(const float* __rest
     const int c0 = (bx * WAVES + wave) * 256;
     // `full` with ONE 16-wave workgroup per rank block (N <= 4096): the row of W is collected in LDS, by column rank, and leaves as
     // one coalesced write -- N scattered 8-byte stores per row block otherwise (the triangle alone is half of them)
-    __shared__ u64 rowbuf[(WAVES == 16) ? 4096 : 1];
+    __shared__ __attribute__((aligned(16))) u64 rowbuf[(WAVES == 16) ? 4096 : 1];
     const bool rowbuffered = WAVES == 16 && full && gridDim.x == 1 && L.NC <= 4096;
     if (k0 >= n) return;                                                 // (workgroup-uniform)
     ImgPtrs I = img_ptrs(ws, L, b);
@@ -964,7 +981,8 @@ __global__ __launch_bounds__(WAVES * 64) void bitmask_kernel(const float* __rest
             if (col[j] < L.NC && rk[j] >= 0 && rk[j] < L.NC) rowbuf[rk[j]] = w;
         }
         __syncthreads();
-        for (int i = threadIdx.x; i < L.NC; i += WAVES * 64) Wk[i] = rowbuf[i];
+        if (wt) w_rows_write_through(Wk, rowbuf, L.NC);
+        else for (int i = threadIdx.x; i < L.NC; i += WAVES * 64) Wk[i] = rowbuf[i];
         return;
     }
 #pragma unroll
@@ -1135,7 +1153,7 @@ __device__ __forceinline__ float wave_max_f(float v) { return gnms_wave_max_f(v)
 // (the scan pulls), so the scatter version issues N^2 / 64 scattered 8-byte stores per image -- 256 MB per step at B = 8, N = 16384.
 template <int CPL, int KBW, bool ROWBUF, bool CHUNKLOOP = false>
 __device__ __forceinline__ void bitmask_boxes_body(const float* __restrict__ boxes, int N, const int* __restrict__ counts, float thr, char* ws,
-                                                   gnms_ws_layout L, const int b, const int bx) {
+                                                   gnms_ws_layout L, const int b, const int bx, const int wt = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = gnms_count(counts, b, N);
     constexpr int kCols = 64 * CPL;
@@ -1393,6 +1411,12 @@ __device__ __forceinline__ void bitmask_boxes_body(const float* __restrict__ box
     if (ROWBUF) {
         __syncthreads();
         GNMS_BT();
+        if (wt) {                                                      // (wave-uniform: a kernel argument)
+            // the rows of the workgroup's live rank blocks as ONE span, written through (w_rows_write_through); block bx * KBW is live here
+            int live = 1;
+            while (live < KBW && bx * KBW + live < L.NB && (bx * KBW + live) * 64 < n) ++live;
+            w_rows_write_through(I.W + (size_t)bx * KBW * L.NC, rowbuf, live * L.NC);
+        } else
         for (int kw = 0; kw < KBW; ++kw) {
             const int kb = bx * KBW + kw;
             if (kb >= L.NB || kb * 64 >= n) break;
@@ -1418,8 +1442,8 @@ __device__ __forceinline__ void bitmask_boxes_body(const float* __restrict__ box
 // (ROWBUF without the chunk loop: two 16-wave workgroups per CU = 8 waves per SIMD, i.e. at most 64 VGPRs -- asked for explicitly)
 template <int CPL, int KBW, bool ROWBUF = false, bool CHUNKLOOP = false>
 __global__ __launch_bounds__(ROWBUF ? 1024 : 256, (ROWBUF && !CHUNKLOOP) ? (KBW > 1 ? 4 : 8) : 1) void bitmask_boxes_kernel(const float* __restrict__ boxes, int N, const int* __restrict__ counts,
-                                                            float thr, char* ws, gnms_ws_layout L) {
-    bitmask_boxes_body<CPL, KBW, ROWBUF, CHUNKLOOP>(boxes, N, counts, thr, ws, L, (int)blockIdx.z, (int)blockIdx.x);
+                                                            float thr, char* ws, gnms_ws_layout L, int wt) {
+    bitmask_boxes_body<CPL, KBW, ROWBUF, CHUNKLOOP>(boxes, N, counts, thr, ws, L, (int)blockIdx.z, (int)blockIdx.x, wt);
 }
 
 // The scatter variant (no LDS row) with the row groups dealt to the XCDs, as bitmask_rec3d_culled_kernel does (round 4b): workgroup x runs on

@@ -366,6 +366,18 @@ int check_common(const char* fn, int B, int N, int64_t ld, const gnms_params* P,
 // The matrix-in layer decides on the device whether the thresholded matrix is symmetric (every caller in the reference passes
 // iou(boxes, boxes)): bitmask_kernel then stores the rows of W in full and wsym_check_kernel compares the 64 x 64 blocks with
 // their transposes; K3 / K4 (sym = 2) take the pulling, attributing scan for the images that pass.  GNMS_MATRIX_SYM=0: never.
+// The row-buffer kernels' rows of W leave as 16-byte write-through stores (w_rows_write_through, nms_kernels.h) on the routes in this mask.
+// GNMS_W_WRITE_THROUGH=0: plain stores everywhere (developer / test switch, read once: both forms stay reachable in one build for A/B runs
+// and the tests); another number is taken as the mask itself (kWtKbw2 = 1, kWtKbw1 = 2, kWtChunkLoop = 4, kWtMatrixIn = 8), for A/B runs
+// of a single route.
+// Measured per route (LABNOTES R9, ms per step, three alternating runs, parent / change): two blocks per workgroup (B = 8, N = 4096) 0.1317-0.1318 /
+// 0.1290-0.1291; one block (B = 4) 0.0833-0.0836 / 0.0809-0.0818; matrix-in (--two-calls) 0.2362-0.2379 / 0.2352-0.2361.  The chunk loop
+// (B = 32, N = 4096: W is 67 MB, twice the L2, and streams through it anyway) shows no difference between the two forms and keeps the plain store.
+constexpr int kWtDefaultRoutes = kWtKbw2 | kWtKbw1 | kWtMatrixIn;
+int w_write_through_routes() {
+    static const int routes = [] { const char* e = getenv("GNMS_W_WRITE_THROUGH"); return e && e[0] ? atoi(e) : kWtDefaultRoutes; }();
+    return routes;
+}
 bool matrix_sym_detection(int N) {
     static const int forced = [] { const char* e = getenv("GNMS_MATRIX_SYM"); return e ? atoi(e) : -1; }();
     return forced >= 0 ? forced != 0 : N >= 256;
@@ -375,8 +387,9 @@ int launch_bitmask(const float* iou, int B, int N, int64_t ld, const int32_t* co
     // (measured at B = 8, N = 4096, three interleaved repetitions: 16 waves 91.6-91.8 us = 0.733 of the HBM peak, 8 waves 95.2-95.7 us;
     // 16 loads in flight per wave change nothing either way)
     const bool vec = (ld % 4 == 0) && ((uintptr_t)iou % 16 == 0);
+    const int wt = w_write_through_routes() & kWtMatrixIn;           // (only the 16-wave kernel has the row buffer)
 #define GNMS_BITMASK(V, W, R)                                                                                                         \
-    gnms_launch_prof(kProfMatrixRead, bitmask_kernel<V, W, R>, dim3(gnms_div_up(N, W * 256), L.NB, B), dim3(W * 64), 0, st, iou, N, (long)ld, counts, thr, ws, L, full)
+    gnms_launch_prof(kProfMatrixRead, bitmask_kernel<V, W, R>, dim3(gnms_div_up(N, W * 256), L.NB, B), dim3(W * 64), 0, st, iou, N, (long)ld, counts, thr, ws, L, full, wt)
     // few, small images: one batch of loads per wave instead of eight in a row (bitmask_small_kernel)
     constexpr int small_wgs = 1024;
     if (!vec) GNMS_BITMASK(false, kMaskWaves, kMaskRB);
@@ -967,6 +980,7 @@ __global__ __launch_bounds__(1024) void one_launch_boxes_kernel(const float* __r
 int launch_bitmask_boxes(const float* boxes, int B, int N, const int32_t* counts, float thr, char* ws, const gnms_ws_layout& L, hipStream_t st) {
     const int NB = (N + 63) / 64;
     const long long tiles4 = (long long)B * NB * ((N + 255) / 256);
+    const int wt = w_write_through_routes();
     if (N > 4096 && N % 1024 == 0) {
         // large images (round 4b): the scatter kernel with the row groups dealt to the XCDs (bitmask_boxes_pinned_kernel) -- a row of W is
         // >= 64 KiB here and completing its lines in ONE L2 costs less than collecting it in LDS first (one 16-wave workgroup per CU):
@@ -983,7 +997,7 @@ int launch_bitmask_boxes(const float* boxes, int B, int N, const int32_t* counts
         const size_t lds = (size_t)L.NC * 8;
         int rc = allow_lds(bitmask_boxes_kernel<4, 1, true, true>, lds);
         if (rc) return rc;
-        bitmask_boxes_kernel<4, 1, true, true><<<dim3(NB, 1, B), 1024, lds, st>>>(boxes, N, counts, thr, ws, L);
+        bitmask_boxes_kernel<4, 1, true, true><<<dim3(NB, 1, B), 1024, lds, st>>>(boxes, N, counts, thr, ws, L, wt & kWtChunkLoop);
     } else if (tiles4 >= 2048 && (N + 255) / 256 <= 16) {
         // one 16-wave workgroup per rank block: words collected in an LDS copy of the row, written out coalesced
         // (from two workgroups per CU on: two rank blocks per workgroup -- half the column-side traffic, one workgroup per CU; see the body)
@@ -991,13 +1005,13 @@ int launch_bitmask_boxes(const float* boxes, int B, int N, const int32_t* counts
             const size_t lds = 2 * (size_t)L.NC * 8;                   // (the ranks stay in registers here: no stash)
             int rc = allow_lds(bitmask_boxes_kernel<4, 2, true>, lds);
             if (rc) return rc;
-            bitmask_boxes_kernel<4, 2, true><<<dim3((NB + 1) / 2, 1, B), 1024, lds, st>>>(boxes, N, counts, thr, ws, L);
+            bitmask_boxes_kernel<4, 2, true><<<dim3((NB + 1) / 2, 1, B), 1024, lds, st>>>(boxes, N, counts, thr, ws, L, wt & kWtKbw2);
         } else
-        bitmask_boxes_kernel<4, 1, true><<<dim3(NB, 1, B), 1024, (size_t)L.NC * 8 + 4 * 1024 * sizeof(int), st>>>(boxes, N, counts, thr, ws, L);   // + the ranks' stash
+        bitmask_boxes_kernel<4, 1, true><<<dim3(NB, 1, B), 1024, (size_t)L.NC * 8 + 4 * 1024 * sizeof(int), st>>>(boxes, N, counts, thr, ws, L, wt & kWtKbw1);   // + the ranks' stash
     } else if (tiles4 >= 2048) {
-        bitmask_boxes_kernel<4, 1><<<dim3(gnms_div_up(NB * ((N + 255) / 256), 4), 1, B), 256, 0, st>>>(boxes, N, counts, thr, ws, L);
+        bitmask_boxes_kernel<4, 1><<<dim3(gnms_div_up(NB * ((N + 255) / 256), 4), 1, B), 256, 0, st>>>(boxes, N, counts, thr, ws, L, 0);
     } else {
-        bitmask_boxes_kernel<1, 1><<<dim3(gnms_div_up(NB * NB, 4), 1, B), 256, 0, st>>>(boxes, N, counts, thr, ws, L);
+        bitmask_boxes_kernel<1, 1><<<dim3(gnms_div_up(NB * NB, 4), 1, B), 256, 0, st>>>(boxes, N, counts, thr, ws, L, 0);
     }
     GNMS_CHECK_LAUNCH();
     return GNMS_OK;
