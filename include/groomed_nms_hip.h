@@ -556,6 +556,46 @@ int gnms_kitti_rows_append(const float* det, int det_cols, const int32_t* counts
  * element that is not finite or not below 1e9 in magnitude (copied as it is). */
 int gnms_round6(const double* in, double* out, int64_t n, int64_t* outside_count, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Between gnms_compute_targets and the NMS block of the training loss: the hard-anchor sampling, the sample weights and the weighted
+ * classification term (lib/loss/rpn_3d.py:458-472, 583-612, 885-1001), csrc/sampling.hip, DESIGN.md 3.14.  Stream-ordered launches
+ * only, no allocation, no global atomics, no workgroup waits for another: graph-capturable, and the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------------ */
+#define GNMS_SAMPLE_IGN_FLAG 3000     /* labels of ignored anchors (IGN_FLAG, :184) */
+#define GNMS_SAMPLE_COUNT_COLS 6      /* n_fg, n_bg, fg_num, bg_num (the reference's quotas, :583-588), sampled fg, sampled bg */
+/* target_labels: column 4 of the targets rows, anchor r of image b at target_labels[(b * R + r) * ld_target_labels] (t > 0: foreground
+ * of class (int)t, t < 0: background, t == 0: ignore; a class outside [1, C) counts as ignore, a NaN as "label 0, never sampled").
+ * prob [B][R][C] (column 0 = background).  skip [B] bytes or NULL: a nonzero byte is an image without a valid ground truth (:406):
+ * its labels are 0, nothing of it is sampled, its labels_scores are 0.
+ * Quotas per image (:583-588): box_samples = +inf keeps everything; else fg_num = min(round(R box_samples fg_fraction), n_fg) and
+ * bg_num = min(round(R box_samples - fg_num), n_bg), round = half to even on float64.  A class is cut to its quota only when
+ * 0 < quota != members (:591, :597) -- a quota of 0 keeps the whole class -- and then keeps the anchors with the smallest
+ * prob[b][r][label] (NaN last; among equal keys the lower anchor index first).
+ * Outputs (all required, every element written): labels [B][R] int64 (0, the class, GNMS_SAMPLE_IGN_FLAG), bbox_weights [B][R]
+ * (1 on the sampled foreground), labels_scores [B][R] (prob[b][r][labels] where labels is not the ignore flag), sampled [B][R]
+ * bytes (0 no, 1 foreground, 2 background), fg_index [B][R] int32: the sampled foreground in ascending anchor order, -1 behind
+ * fg_counts[b] (gnms_select_topk's candidates / candidate_counts), counts [B][GNMS_SAMPLE_COUNT_COLS] int32.
+ * workspace: gnms_sample_anchors_workspace_bytes(B, R) bytes, 16-byte aligned, every byte written before it is read. */
+size_t gnms_sample_anchors_workspace_bytes(int B, int R);
+int gnms_sample_anchors(const float* target_labels, int64_t ld_target_labels, const float* prob, const uint8_t* skip, int B, int R,
+                        int C, double box_samples, int has_fg_fraction, double fg_fraction, int64_t* labels, float* bbox_weights,
+                        float* labels_scores, uint8_t* sampled, int32_t* fg_index, int32_t* fg_counts, int32_t* counts,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* :913-1001 from gnms_sample_anchors' outputs and the logits cls [B][R][C].  Weights (:913-961): 1 on every sampled anchor, the
+ * foreground (has_fg_fraction and a sampled foreground in the batch) (f / (1 - f)) * (sampled bg / sampled fg) over the batch;
+ * focal_loss != 0: times (1 - labels_scores) ** focal_loss; all in float64, rounded once into labels_weight [B][R].
+ * Term (:976-1001): over the anchors with labels_weight > 0, cross entropy of the float32 log-softmax times the weight, clamped to
+ * [0, 2000], summed in float64, mean rounded to float32, times cls_2d_lambda -> loss [1] (0 without an active anchor or with
+ * cls_2d_lambda == 0).  dcls [B][R][C] = dloss / dcls (0 on inactive anchors and where the weighted loss left the clamp).
+ * acc [2] float64 = accuracy of argmax(cls) over all foreground-labelled anchors / all anchors labelled 0 (:893-907; NaN when there
+ * is none); stat_counts [5] int32 = fg correct, fg all, bg correct, bg all, active anchors.
+ * workspace: gnms_cls_loss_workspace_bytes(B, R) bytes, 8-byte aligned. */
+size_t gnms_cls_loss_workspace_bytes(int B, int R);
+int gnms_cls_loss(const float* cls, const int64_t* labels, const float* labels_scores, const uint8_t* sampled, const int32_t* counts,
+                  int B, int R, int C, int has_fg_fraction, double fg_fraction, double focal_loss, double cls_2d_lambda,
+                  float* labels_weight, float* loss, float* dcls, double* acc, int32_t* stat_counts, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
