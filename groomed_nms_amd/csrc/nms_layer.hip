@@ -122,21 +122,6 @@ __global__ __launch_bounds__(512) void prof_read_kernel(const float4* __restrict
     }
     if (acc == 123456.789f) *sink = acc;                          // never true for the data it is run on; keeps the loads alive
 }
-int device_cu_count() {
-    static std::mutex mu;
-    static std::map<int, int> cus;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    std::lock_guard<std::mutex> lock(mu);
-    int& c = cus[dev];
-    if (c == 0) {
-        hipDeviceProp_t prop;
-        c = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return c;
-}
-
-
 // the same bytes in the geometry of the matrix writers: a wave stores ROWS rows x 1 KiB (rows `ld` floats apart), 16 waves side by side,
 // one workgroup per CU walking the row bands -- no loads, no arithmetic
 template <int ROWS, bool NT>
@@ -173,14 +158,27 @@ __global__ __launch_bounds__(1024) void prof_fill_tiles_kernel(float* __restrict
     }
 }
 }  // namespace
-int gnms_device_cu_count() { return device_cu_count(); }
+// compute units of the current device, cached per device (declared in gnms_common.h)
+int gnms_device_cu_count() {
+    static std::mutex mu;
+    static std::map<int, int> cus;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    std::lock_guard<std::mutex> lock(mu);
+    int& c = cus[dev];
+    if (c == 0) {
+        hipDeviceProp_t prop;
+        c = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+    }
+    return c;
+}
 extern "C" int gnms_profile_fill_tiles(float* dst, int B, int N, int64_t ld, int rows, int nontemporal, void* stream) {
     GNMS_CHECK_ARG(dst && B > 0 && N > 0 && ld >= N && ld % 4 == 0 && (uintptr_t)dst % 16 == 0,
                    "gnms_profile_fill_tiles: dst 16-byte aligned, ld >= N a multiple of 4");
     GNMS_CHECK_ARG((rows == 4 || rows == 8 || rows == 16 || rows == 32 || rows == 64) && N % rows == 0,
                    "gnms_profile_fill_tiles: rows per wave tile must be 4, 8, 16, 32 or 64 and divide N (rows=%d N=%d)", rows, N);
     const int order = 0;                                           // row band major (the other orders of round 2 measured slower: LABNOTES.md)
-    const dim3 grid((unsigned)device_cu_count());
+    const dim3 grid((unsigned)gnms_device_cu_count());
     hipStream_t st = (hipStream_t)stream;
     const long bands = (long)B * N / rows;
 #define GNMS_FILL_TILES(R)                                                                                                                  \
@@ -247,7 +245,7 @@ extern "C" int gnms_profile_fill_sym(float* dst, int B, int N, int64_t ld, int t
     hipStream_t st = (hipStream_t)stream;
     const int nt = N / tile;
     const long total = (long)nt * (nt + 1) / 2 * B;
-    const dim3 grid((unsigned)(persist ? device_cu_count() * (tile == 128 ? 2 : 1) : total));
+    const dim3 grid((unsigned)(persist ? gnms_device_cu_count() * (tile == 128 ? 2 : 1) : total));
     const dim3 block(tile == 128 ? 512 : 1024);
 #define GNMS_FILL_SYM(TT, CC)                                                                                                              \
     do {                                                                                                                                   \
@@ -329,9 +327,8 @@ int next_pow2(int n) {
 
 size_t leaders_lds_bytes(int N) { return leaders_lds_size((N + 63) / 64); }
 
-int allow_lds_raw(const void* kernel, size_t bytes) { return gnms_allow_lds_raw(kernel, bytes); }
 template <typename K>
-int allow_lds(K kernel, size_t bytes) { return allow_lds_raw(reinterpret_cast<const void*>(kernel), bytes); }
+int allow_lds(K kernel, size_t bytes) { return gnms_allow_lds_raw(reinterpret_cast<const void*>(kernel), bytes); }
 
 int check_common(const char* fn, int B, int N, int64_t ld, const gnms_params* P, const void* ws, size_t ws_bytes) {
     GNMS_CHECK_ARG(P != nullptr, "%s: params is NULL", fn);
@@ -374,53 +371,154 @@ int check_common(const char* fn, int B, int N, int64_t ld, const gnms_params* P,
 // 0.1290-0.1291; one block (B = 4) 0.0833-0.0836 / 0.0809-0.0818; matrix-in (--two-calls) 0.2362-0.2379 / 0.2352-0.2361.  The chunk loop
 // (B = 32, N = 4096: W is 67 MB, twice the L2, and streams through it anyway) shows no difference between the two forms and keeps the plain store.
 constexpr int kWtDefaultRoutes = kWtKbw2 | kWtKbw1 | kWtMatrixIn;
-int w_write_through_routes() {
-    static const int routes = [] { const char* e = getenv("GNMS_W_WRITE_THROUGH"); return e && e[0] ? atoi(e) : kWtDefaultRoutes; }();
-    return routes;
-}
+// A developer / test switch: the number in the environment variable `name`, `dflt` where it is unset or empty.  Every switch reads its
+// variable once, into a function-local static, so both forms of what it selects stay reachable in one build for A/B runs and the tests.
+int env_switch(const char* name, int dflt) { const char* e = getenv(name); return e && e[0] ? atoi(e) : dflt; }
+int w_write_through_routes() { static const int routes = env_switch("GNMS_W_WRITE_THROUGH", kWtDefaultRoutes); return routes; }
 bool matrix_sym_detection(int N) {
-    static const int forced = [] { const char* e = getenv("GNMS_MATRIX_SYM"); return e ? atoi(e) : -1; }();
+    static const int forced = env_switch("GNMS_MATRIX_SYM", -1);
     return forced >= 0 ? forced != 0 : N >= 256;
 }
+
+// What every launcher of the layer is handed: the sizes, the workspace, the stream and the outputs of one call.
+struct LayerCall {
+    int B, N;
+    const int32_t* counts;
+    gnms_params P;
+    gnms_ws_layout L;
+    char* ws;
+    hipStream_t st;
+    int P2;                                                       // keys of the block sorts: next_pow2(N)
+    float* prob;
+    int64_t *order, *valid, *invalid;
+    int32_t *nvalid, *ninvalid;
+    size_t sort_lds() const { return (size_t)P2 * 8; }
+    int sort_threads() const { return P2 <= 1024 ? P2 : 1024; }
+};
+LayerCall make_call(int B, int N, const int32_t* counts, const gnms_params& P, void* workspace, void* stream, float* prob = nullptr,
+                    int64_t* order = nullptr, int64_t* valid = nullptr, int64_t* invalid = nullptr, int32_t* nvalid = nullptr,
+                    int32_t* ninvalid = nullptr) {
+    return LayerCall{B, N, counts, P, gnms_make_layout(N), (char*)workspace, (hipStream_t)stream, next_pow2(N), prob, order, valid, invalid, nvalid, ninvalid};
+}
+// The prologue of an entry: the checks, then the call.  kCallEmpty (> 0: not an error code): nothing to launch -- B == 0, or N == 0, where the
+// counts the call has are zeroed.  without_matrix: an entry that has the boxes only, the grouped hard-sorted modes; ptrs_ok: the entry's own
+// pointers are all there (asked only of a call that is not empty; null_msg says which entry).
+constexpr int kCallEmpty = 1;
+int begin_call(const char* fn, LayerCall* c, int B, int N, int64_t ld, const int32_t* counts, const gnms_params* params, void* workspace,
+               size_t workspace_bytes, void* stream, bool without_matrix, bool ptrs_ok, const char* null_msg, float* prob = nullptr,
+               int64_t* order = nullptr, int64_t* valid = nullptr, int64_t* invalid = nullptr, int32_t* nvalid = nullptr, int32_t* ninvalid = nullptr) {
+    int rc = check_common(fn, B, N, ld, params, workspace, workspace_bytes);
+    if (rc) return rc;
+    if (without_matrix && (!params->group_boxes || params->presorted)) {
+        gnms_set_error("%s: only the grouped, hard-sorted modes run without the matrix", fn);
+        return GNMS_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 0) return kCallEmpty;
+    if (N == 0) {
+        if (nvalid) GNMS_CHECK_HIP(hipMemsetAsync(nvalid, 0, sizeof(int32_t) * B, st));
+        if (ninvalid) GNMS_CHECK_HIP(hipMemsetAsync(ninvalid, 0, sizeof(int32_t) * B, st));
+        return kCallEmpty;
+    }
+    GNMS_CHECK_ARG(ptrs_ok, "%s", null_msg);
+    *c = make_call(B, N, counts, *params, workspace, stream, prob, order, valid, invalid, nvalid, ninvalid);
+    return GNMS_OK;
+}
+// the entries return through this: an empty call is a success
+#define GNMS_BEGIN_CALL(...)                                      \
+    do {                                                          \
+        const int rc__ = begin_call(__VA_ARGS__);                 \
+        if (rc__) return rc__ == kCallEmpty ? GNMS_OK : rc__;     \
+    } while (0)
+
+// the direction of the per-group solves (solve_groups_kernel's BWD)
+constexpr bool kForward = false, kBackward = true;
+
 // full: 0 = only the words a leader scan reads; 1 = whole rows + wsym_check_kernel behind; 2 = whole rows, the check rides in the tail launch
-int launch_bitmask(const float* iou, int B, int N, int64_t ld, const int32_t* counts, float thr, char* ws, const gnms_ws_layout& L, hipStream_t st, int full = 0) {
+int launch_bitmask(const LayerCall& c, const float* iou, int64_t ld, int full = 0) {
+    const int B = c.B, N = c.N;
+    const gnms_ws_layout& L = c.L;
     // (measured at B = 8, N = 4096, three interleaved repetitions: 16 waves 91.6-91.8 us = 0.733 of the HBM peak, 8 waves 95.2-95.7 us;
     // 16 loads in flight per wave change nothing either way)
     const bool vec = (ld % 4 == 0) && ((uintptr_t)iou % 16 == 0);
     const int wt = w_write_through_routes() & kWtMatrixIn;           // (only the 16-wave kernel has the row buffer)
 #define GNMS_BITMASK(V, W, R)                                                                                                         \
-    gnms_launch_prof(kProfMatrixRead, bitmask_kernel<V, W, R>, dim3(gnms_div_up(N, W * 256), L.NB, B), dim3(W * 64), 0, st, iou, N, (long)ld, counts, thr, ws, L, full, wt)
+    gnms_launch_prof(kProfMatrixRead, bitmask_kernel<V, W, R>, dim3(gnms_div_up(N, W * 256), L.NB, B), dim3(W * 64), 0, c.st, iou, N, (long)ld, c.counts, c.P.nms_threshold, c.ws, L, full, wt)
     // few, small images: one batch of loads per wave instead of eight in a row (bitmask_small_kernel)
     constexpr int small_wgs = 1024;
     if (!vec) GNMS_BITMASK(false, kMaskWaves, kMaskRB);
     else if (N <= 2048 && (long)B * L.NB * gnms_div_up(N, 256) <= (long)small_wgs)        // (N = 4096, B = 1 keeps the row-buffered 16-wave kernel)
-        gnms_launch_prof(kProfMatrixRead, bitmask_small_kernel, dim3(gnms_div_up(N, 256), L.NB, B), dim3(512), 0, st, iou, N, (long)ld, counts, thr, ws, L, full);
+        gnms_launch_prof(kProfMatrixRead, bitmask_small_kernel, dim3(gnms_div_up(N, 256), L.NB, B), dim3(512), 0, c.st, iou, N, (long)ld, c.counts, c.P.nms_threshold, c.ws, L, full);
     else if (N >= 4096) GNMS_BITMASK(true, 16, 8);
     else GNMS_BITMASK(true, 8, 8);
 #undef GNMS_BITMASK
     GNMS_CHECK_LAUNCH();
     if (full == 1) {
         const int nb = (N + 63) / 64;
-        wsym_check_kernel<<<dim3(gnms_div_up(nb * (nb + 1) / 2, 4), B), 256, 0, st>>>(N, counts, ws, L);
+        wsym_check_kernel<<<dim3(gnms_div_up(nb * (nb + 1) / 2, 4), B), 256, 0, c.st>>>(N, c.counts, c.ws, L);
         GNMS_CHECK_LAUNCH();
     }
     return GNMS_OK;
 }
 
-// grouping pipeline K2..K4 (shared by gnms_forward and gnms_get_groups)
-int run_grouping(const float* iou, int B, int N, int64_t ld, const int32_t* counts, float thr, char* ws, const gnms_ws_layout& L,
-                 hipStream_t st) {
-    const int sym = matrix_sym_detection(N) ? 2 : 0;
-    int rc0 = launch_bitmask(iou, B, N, ld, counts, thr, ws, L, st, sym ? 1 : 0);
-    if (rc0) return rc0;
-    const size_t lds = leaders_lds_bytes(N);
+// ------------------------------------------------------------------------------------------------
+// K3..K6 as launches of their own, one launcher per block; src / ld: the overlaps' source (SRC: kFromMatrix, kFromBoxes, kFromRecords)
+// ------------------------------------------------------------------------------------------------
+// K3 + K4: the leader scan and the attribution, behind the bit matrix
+template <int SRC>
+int launch_leaders_attribute(const LayerCall& c, const float* src, int64_t ld, int sym) {
+    const size_t lds = leaders_lds_bytes(c.N);
     int rc = allow_lds(leaders_kernel, lds);
     if (rc) return rc;
-    { const int spw = leaders_chain_wgs(N, sym); leaders_kernel<<<B * spw, 1024, lds, st>>>(N, counts, ws, L, sym, B, spw); }
+    const int spw = leaders_chain_wgs(c.N, sym);
+    leaders_kernel<<<c.B * spw, 1024, lds, c.st>>>(c.N, c.counts, c.ws, c.L, sym, c.B, spw);
     GNMS_CHECK_LAUNCH();
-    attribute_kernel<false><<<dim3(L.NB, B), 64, 0, st>>>(iou, (long)ld, N, counts, thr, ws, L, sym);
+    attribute_kernel<SRC><<<dim3(c.L.NB, c.B), 64, 0, c.st>>>(src, (long)ld, c.N, c.counts, c.P.nms_threshold, c.ws, c.L, sym);
     GNMS_CHECK_LAUNCH();
     return GNMS_OK;
+}
+// K5
+template <int SRC>
+int launch_groups(const LayerCall& c, const float* src, int64_t ld) {
+    int rc;
+    GNMS_DISPATCH_SORT(c.P2, {
+        if ((rc = allow_lds(groups_kernel<E, SRC>, c.sort_lds()))) return rc;
+        groups_kernel<E, SRC><<<c.B, c.sort_threads(), c.sort_lds(), c.st>>>(src, c.N, (long)ld, c.counts, c.P, c.ws, c.L, c.P2);
+    });
+    GNMS_CHECK_LAUNCH();
+    return GNMS_OK;
+}
+// unmasked groups: the per-group solves, forward (between K5 and K6) and backward
+template <bool BWD, int SRC>
+int launch_solve_groups(const LayerCall& c, const float* src, int64_t ld, float* grad_scores, float* grad_src) {
+    int rc;
+    if ((rc = allow_lds(solve_groups_kernel<BWD, SRC == kFromBoxes>, kSolveGroupsLds))) return rc;
+    solve_groups_kernel<BWD, SRC == kFromBoxes><<<dim3(solve_groups_wgs(c.B, gnms_device_cu_count()), c.B), 1024, kSolveGroupsLds, c.st>>>(
+        src, c.N, (long)ld, c.counts, c.P, c.ws, c.L, grad_scores, grad_src);
+    GNMS_CHECK_LAUNCH();
+    return GNMS_OK;
+}
+// K6
+int launch_finalize(const LayerCall& c) {
+    int rc;
+    GNMS_DISPATCH_SORT(c.P2, {
+        if ((rc = allow_lds(finalize_kernel<E>, c.sort_lds()))) return rc;
+        finalize_kernel<E><<<c.B, c.sort_threads(), c.sort_lds(), c.st>>>(c.N, c.counts, c.P, c.ws, c.L, c.P2, c.prob, (long long*)c.valid, (long long*)c.invalid,
+                                                                            c.nvalid, c.ninvalid);
+    });
+    GNMS_CHECK_LAUNCH();
+    return GNMS_OK;
+}
+// K3..K6 behind the bit matrix, where they do not run as one launch (launch_tail, launch_tail_write)
+template <int SRC>
+int launch_separate_tail(const LayerCall& c, const float* src, int64_t ld, int sym) {
+    int rc;
+    if ((rc = launch_leaders_attribute<SRC>(c, src, ld, sym))) return rc;
+    if ((rc = launch_groups<SRC>(c, src, ld))) return rc;
+    if constexpr (SRC != kFromRecords) {                          // (the from-records layer runs masked groups only)
+        if (!c.P.mask_group_boxes && (rc = launch_solve_groups<kForward, SRC>(c, src, ld, nullptr, nullptr))) return rc;
+    }
+    return launch_finalize(c);
 }
 
 }  // namespace
@@ -731,7 +829,7 @@ __global__ __launch_bounds__(1024) void write_staged_kernel(const float* __restr
 
 // the launch; reserve: CUs left without a writer workgroup for the layer's one-workgroup-per-image kernels on the caller's stream
 int launch_write_staged(const float* a, const float* b, int B, int M, int N, float* out, int64_t ld, int reserve, hipStream_t st) {
-    const int cus = device_cu_count();
+    const int cus = gnms_device_cu_count();
     int grid = cus - reserve;
     if (grid < cus / 2) grid = cus / 2;
     const size_t lds = 96 * 1024;                                    // > 80 KiB: one writer workgroup per CU (it uses 4096 + 32 boxes = 64.5 KiB)
@@ -748,13 +846,13 @@ bool gnms_internal_iou2d_wants_staged(int B, int M, int N, int64_t ld, const flo
     // (N <= 4096: the per-unit row fetch and barrier cost more than the geometry gains -- B = 8, M = N = 4096: 108-114 us against the
     // 64-row tiles' 102; N = 16384: 1.61 ms against 1.85)
     const long units = (long)B * ((M + kStagedRows - 1) / kStagedRows) * ((N + 4095) / 4096);
-    return N > 4096 && units >= 4L * device_cu_count();
+    return N > 4096 && units >= 4L * gnms_device_cu_count();
 }
 // a == b, N <= 4096: iou2d_self_kernel (B = 8, N = 4096: 0.68-0.69 -> 0.71 of the HBM peak)
 bool gnms_internal_iou2d_wants_self(const float* a, const float* b, int B, int M, int N, int64_t ld, const float* out) {
     if (a != b || M != N || N > 4096 || B > 127) return false;
     const long units = (long)B * ((N + kStagedRows - 1) / kStagedRows) * ((N + 4095) / 4096);
-    return units >= 8L * device_cu_count();
+    return units >= 8L * gnms_device_cu_count();
 }
 namespace {
 // The claim counters of iou2d_self_kernel live in zeroed SLOTS of a per-device pool that the library allocates once (the first eager call on
@@ -814,7 +912,7 @@ int claim_slot_for(hipStream_t st, int** slot) {
 }  // namespace
 // (returns 1 -- not an error -- when no claim slot is to be had: gnms_iou2d then runs iou2d_kernel)
 int gnms_internal_iou2d_self(const float* boxes, int B, int N, float* out, int64_t ld, hipStream_t st) {
-    const int cus = device_cu_count();
+    const int cus = gnms_device_cu_count();
     int grid = cus - 8;                                              // (alone on the machine the stream likes every CU: 248 -> 0.71, 200 -> 0.64)
     if (grid < 1) grid = 1;
     int* claims = nullptr;
@@ -977,7 +1075,9 @@ __global__ __launch_bounds__(1024) void one_launch_boxes_kernel(const float* __r
 
 // bitmask_boxes_kernel: workgroups of 4 wave tiles, (row blocks) x (column chunks) tiles per image; 4 columns per lane
 // (64 x 256 tiles) when that already gives every SIMD a couple of waves, else 1 column per lane (64 x 64 tiles)
-int launch_bitmask_boxes(const float* boxes, int B, int N, const int32_t* counts, float thr, char* ws, const gnms_ws_layout& L, hipStream_t st) {
+int launch_bitmask_boxes(const LayerCall& c, const float* boxes) {
+    const int B = c.B, N = c.N;
+    const gnms_ws_layout& L = c.L;
     const int NB = (N + 63) / 64;
     const long long tiles4 = (long long)B * NB * ((N + 255) / 256);
     const int wt = w_write_through_routes();
@@ -988,8 +1088,8 @@ int launch_bitmask_boxes(const float* boxes, int B, int N, const int32_t* counts
         // (16384: 288 / 217 / 189 / 184 us with 1 / 2 / 4 / 8).
         const int kbw = tiles4 >= 32768 ? 4 : 1;
         const unsigned gx = (unsigned)(gnms_div_up(gnms_div_up(NB, kbw), 8) * (((N + 255) / 256) / 4) * 8);
-        if (kbw >= 4) bitmask_boxes_pinned_kernel<4><<<dim3(gx, 1, B), 256, 0, st>>>(boxes, N, counts, thr, ws, L);
-        else bitmask_boxes_pinned_kernel<1><<<dim3(gx, 1, B), 256, 0, st>>>(boxes, N, counts, thr, ws, L);
+        if (kbw >= 4) bitmask_boxes_pinned_kernel<4><<<dim3(gx, 1, B), 256, 0, c.st>>>(boxes, N, c.counts, c.P.nms_threshold, c.ws, L);
+        else bitmask_boxes_pinned_kernel<1><<<dim3(gx, 1, B), 256, 0, c.st>>>(boxes, N, c.counts, c.P.nms_threshold, c.ws, L);
     } else if (tiles4 >= 32768) {
         // large images (round 3): the LDS row buffer with a chunk loop -- one 16-wave workgroup per rank block, its waves walking the
         // column chunks, the full row of W leaving as ONE coalesced write (N <= GNMS_MAX_BOXES: the row fits 128 KiB).  The scatter
@@ -997,21 +1097,21 @@ int launch_bitmask_boxes(const float* boxes, int B, int N, const int32_t* counts
         const size_t lds = (size_t)L.NC * 8;
         int rc = allow_lds(bitmask_boxes_kernel<4, 1, true, true>, lds);
         if (rc) return rc;
-        bitmask_boxes_kernel<4, 1, true, true><<<dim3(NB, 1, B), 1024, lds, st>>>(boxes, N, counts, thr, ws, L, wt & kWtChunkLoop);
+        bitmask_boxes_kernel<4, 1, true, true><<<dim3(NB, 1, B), 1024, lds, c.st>>>(boxes, N, c.counts, c.P.nms_threshold, c.ws, L, wt & kWtChunkLoop);
     } else if (tiles4 >= 2048 && (N + 255) / 256 <= 16) {
         // one 16-wave workgroup per rank block: words collected in an LDS copy of the row, written out coalesced
         // (from two workgroups per CU on: two rank blocks per workgroup -- half the column-side traffic, one workgroup per CU; see the body)
-        if ((long)B * NB > (long)device_cu_count()) {
+        if ((long)B * NB > (long)gnms_device_cu_count()) {
             const size_t lds = 2 * (size_t)L.NC * 8;                   // (the ranks stay in registers here: no stash)
             int rc = allow_lds(bitmask_boxes_kernel<4, 2, true>, lds);
             if (rc) return rc;
-            bitmask_boxes_kernel<4, 2, true><<<dim3((NB + 1) / 2, 1, B), 1024, lds, st>>>(boxes, N, counts, thr, ws, L, wt & kWtKbw2);
+            bitmask_boxes_kernel<4, 2, true><<<dim3((NB + 1) / 2, 1, B), 1024, lds, c.st>>>(boxes, N, c.counts, c.P.nms_threshold, c.ws, L, wt & kWtKbw2);
         } else
-        bitmask_boxes_kernel<4, 1, true><<<dim3(NB, 1, B), 1024, (size_t)L.NC * 8 + 4 * 1024 * sizeof(int), st>>>(boxes, N, counts, thr, ws, L, wt & kWtKbw1);   // + the ranks' stash
+        bitmask_boxes_kernel<4, 1, true><<<dim3(NB, 1, B), 1024, (size_t)L.NC * 8 + 4 * 1024 * sizeof(int), c.st>>>(boxes, N, c.counts, c.P.nms_threshold, c.ws, L, wt & kWtKbw1);   // + the ranks' stash
     } else if (tiles4 >= 2048) {
-        bitmask_boxes_kernel<4, 1><<<dim3(gnms_div_up(NB * ((N + 255) / 256), 4), 1, B), 256, 0, st>>>(boxes, N, counts, thr, ws, L, 0);
+        bitmask_boxes_kernel<4, 1><<<dim3(gnms_div_up(NB * ((N + 255) / 256), 4), 1, B), 256, 0, c.st>>>(boxes, N, c.counts, c.P.nms_threshold, c.ws, L, 0);
     } else {
-        bitmask_boxes_kernel<1, 1><<<dim3(gnms_div_up(NB * NB, 4), 1, B), 256, 0, st>>>(boxes, N, counts, thr, ws, L, 0);
+        bitmask_boxes_kernel<1, 1><<<dim3(gnms_div_up(NB * NB, 4), 1, B), 256, 0, c.st>>>(boxes, N, c.counts, c.P.nms_threshold, c.ws, L, 0);
     }
     GNMS_CHECK_LAUNCH();
     return GNMS_OK;
@@ -1019,10 +1119,7 @@ int launch_bitmask_boxes(const float* boxes, int B, int N, const int32_t* counts
 
 // GNMS_RANK_SORT=0: 2048 < N <= 4096 sorts as runs + merge, two launches (developer / test switch, read once: the pair stays reachable for
 // A/B runs and the tests)
-bool rank_sort_enabled() {
-    static const bool on = [] { const char* e = getenv("GNMS_RANK_SORT"); return !(e && e[0] == '0'); }();
-    return on;
-}
+bool rank_sort_enabled() { static const bool on = env_switch("GNMS_RANK_SORT", 1) != 0; return on; }
 
 // K1: stable descending score sort (+ the x-centre sort of the boxes when `boxes` is given).  Which kernels (measured per call in a replayed
 // graph of 20, MI355X, LABNOTES R8.1; W = workgroups of the ranked-runs launch = 16 * B * roles):
@@ -1033,21 +1130,20 @@ bool rank_sort_enabled() {
 // mode3d: 0 = `boxes` are 2D boxes (columns by x centre); >= 1 = pseudo boxes of cuboids whose records lie in the workspace (columns by
 // (z band, x centre) with that many bands; the sort also leaves the records in column order, ImgPtrs::xrec)
 // route (gnms_profile_sorts): 0 = the table above, 1 = runs + merge, 2 = ranked runs
-int launch_sorts(const float* scores, const float* boxes, int B, int N, const int32_t* counts, char* ws, const gnms_ws_layout& L, int P2,
-                 int64_t* order, hipStream_t st, int mode3d = 0, int route = 0) {
+int launch_sorts(const LayerCall& c, const float* scores, const float* boxes, int mode3d = 0, int route = 0) {
+    const int B = c.B, N = c.N, P2 = c.P2;
     int rc;
     const int roles = boxes ? 2 : 1;
     // up to 2048 keys: by counting, N / 64 workgroups per image and role (sort_count_kernel)
-    constexpr bool count_sort = true;
     // (... and up to 4096 keys where its N / 64 workgroups per image and role are ONE round of the machine -- B <= 2 with boxes: 256 compares
     // per thread.  N = 4096 with boxes, us per call: B = 1 counting 7.3, ranked runs 9.7, runs + merge 12.4; B = 2 10.05 / 9.9 / 12.6 -- level
     // with the ranked runs, so the counting sort keeps it; from two rounds on it loses, LABNOTES R5.6)
-    if (route == 0 && count_sort && (N <= 2048 || (N <= 4096 && (long)B * ((N + 63) / 64) * roles <= (long)device_cu_count()))) {
+    if (route == 0 && (N <= 2048 || (N <= 4096 && (long)B * ((N + 63) / 64) * roles <= (long)gnms_device_cu_count()))) {
         const int NP = (N + 63) & ~63;
-        if (NP % 128 == 0 && (long)B * (NP / 32) * roles <= (long)device_cu_count())   // half the compares per thread while the grid is one round
-            sort_count_kernel<32><<<dim3(NP / 32, B, roles), 1024, (size_t)NP * 8, st>>>(scores, boxes, N, counts, ws, L, (long long*)order, mode3d);
+        if (NP % 128 == 0 && (long)B * (NP / 32) * roles <= (long)gnms_device_cu_count())   // half the compares per thread while the grid is one round
+            sort_count_kernel<32><<<dim3(NP / 32, B, roles), 1024, (size_t)NP * 8, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L, (long long*)c.order, mode3d);
         else
-            sort_count_kernel<64><<<dim3(NP / 64, B, roles), 1024, (size_t)NP * 8, st>>>(scores, boxes, N, counts, ws, L, (long long*)order, mode3d);
+            sort_count_kernel<64><<<dim3(NP / 64, B, roles), 1024, (size_t)NP * 8, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L, (long long*)c.order, mode3d);
         GNMS_CHECK_LAUNCH();
         return GNMS_OK;
     }
@@ -1055,18 +1151,18 @@ int launch_sorts(const float* scores, const float* boxes, int B, int N, const in
     // machine.  N = 4096, us per call, ranked runs / runs + merge: with boxes B = 4 10.3 / 12.8, B = 8 11.5 / 13.5, B = 16 (512 workgroups)
     // 16.4 / 15.0; scores alone B = 8 9.5 / 12.4, B = 16 10.3 / 12.7, B = 32 (512 workgroups) 15.4 / 13.9; N = 2112 and 3072 at B = 8 with boxes
     // 10.1 / 12.7 and 10.5 / 13.2.  Every workgroup repeats its image's run sort, so a second round costs more than the second launch saves.
-    if (route == 2 || (route == 0 && P2 == 4096 && rank_sort_enabled() && (long)kRankRuns * B * roles <= (long)device_cu_count())) {
+    if (route == 2 || (route == 0 && P2 == 4096 && rank_sort_enabled() && (long)kRankRuns * B * roles <= (long)gnms_device_cu_count())) {
         if (P2 != 4096) {
             gnms_set_error("launch_sorts: the ranked-runs sort takes 2048 < N <= 4096 (N=%d)", N);
             return GNMS_ERR_UNSUPPORTED;
         }
-        sort_ranked_runs_kernel<<<dim3(kRankRuns, B, roles), 1024, (size_t)kRankRuns * kRankRunKeys * 8, st>>>(scores, boxes, N, counts, ws, L,
-                                                                                                             (long long*)order, mode3d);
+        sort_ranked_runs_kernel<<<dim3(kRankRuns, B, roles), 1024, (size_t)kRankRuns * kRankRunKeys * 8, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L,
+                                                                                                             (long long*)c.order, mode3d);
         GNMS_CHECK_LAUNCH();
         return GNMS_OK;
     }
     if (P2 <= 1024) {
-        sort_scores_kernel<1><<<dim3(B, roles), P2, (size_t)P2 * 8, st>>>(scores, N, counts, ws, L, P2, (long long*)order, boxes, mode3d);
+        sort_scores_kernel<1><<<dim3(B, roles), P2, (size_t)P2 * 8, c.st>>>(scores, N, c.counts, c.ws, c.L, P2, (long long*)c.order, boxes, mode3d);
         GNMS_CHECK_LAUNCH();
         return GNMS_OK;
     }
@@ -1074,12 +1170,12 @@ int launch_sorts(const float* scores, const float* boxes, int B, int N, const in
     const size_t lds = (size_t)P2 * 8;
     // (runs and merge as ONE launch with nonce-flag hand-offs was measured in round 3: 13.1 us against 7.8 + 6.2, the step unchanged -- a launch
     // boundary between two small kernels costs ~1 us; dropped in round 4, LABNOTES.md)
-    sort_runs_kernel<<<dim3(R, B, roles), 1024, 0, st>>>(scores, boxes, N, counts, ws, L, P2, mode3d);
+    sort_runs_kernel<<<dim3(R, B, roles), 1024, 0, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L, P2, mode3d);
     GNMS_CHECK_LAUNCH();
 #define GNMS_MERGE(RR)                                                                                                    \
     do {                                                                                                                  \
         if ((rc = allow_lds(sort_merge_kernel<RR>, lds))) return rc;                                                      \
-        sort_merge_kernel<RR><<<dim3(RR, B, roles), 1024, lds, st>>>(scores, boxes, N, counts, ws, L, (long long*)order, mode3d); \
+        sort_merge_kernel<RR><<<dim3(RR, B, roles), 1024, lds, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L, (long long*)c.order, mode3d); \
     } while (0)
     switch (R) {
         case 2: GNMS_MERGE(2); break;
@@ -1109,36 +1205,38 @@ constexpr int kBesideChainWGs = 1;
 
 // K3..K6 in one launch (masked groups); SRC/src: kFromMatrix (the matrix), kFromBoxes (the boxes), kFromRecords (src unused)
 // the fast tail (nms_kernels.h): on unless GNMS_FAST_TAIL=0 (developer switch: the K5-proper path stays reachable for A/B runs and tests)
-bool fast_tail_enabled() {
-    static const bool on = [] { const char* e = getenv("GNMS_FAST_TAIL"); return !(e && e[0] == '0'); }();
-    return on;
-}
+bool fast_tail_enabled() { static const bool on = env_switch("GNMS_FAST_TAIL", 1) != 0; return on; }
 
-template <int BOXES>
-int launch_tail(const float* src, int B, int N, int64_t ld, const int32_t* counts, const gnms_params& P, char* ws, const gnms_ws_layout& L,
-                float* prob, int64_t* valid, int64_t* invalid, int32_t* nvalid, int32_t* ninvalid, hipStream_t st, int sym, int chain_cap = 0) {
-    int P2 = next_pow2(N);
-    if (P2 < 1024) P2 = 1024;                                   // the fused kernel always runs 1024 threads
+// dynamic LDS of the chain in tail_kernel / tail_write_kernel; P2: the launch's key count (>= 1024: the fused kernels always run 1024 threads)
+size_t tail_lds_bytes(int N, int P2, int fast) {
     // (the fused K5 -> K6 hand-off, E <= 4, parks order[] and a copy of r2 behind the key region: 16 bytes per key)
     const size_t llds = leaders_lds_bytes(N), glds = (size_t)P2 * (P2 <= 4096 ? 16 : 8);
     size_t lds = llds > glds ? llds : glds;
-    const int fast = (fast_tail_enabled() && fast_tail_ok(N, P, sym, chain_cap)) ? 1 : 0;
     if (fast && lds < fast_tail_lds_size(N, P2)) lds = fast_tail_lds_size(N, P2);
+    return lds;
+}
+
+template <int SRC>
+int launch_tail(const LayerCall& c, const float* src, int64_t ld, int sym, int chain_cap = 0) {
+    const int B = c.B, N = c.N;
+    const int P2 = c.P2 < 1024 ? 1024 : c.P2;
+    const int fast = (fast_tail_enabled() && fast_tail_ok(N, c.P, sym, chain_cap)) ? 1 : 0;
+    const size_t lds = tail_lds_bytes(N, P2, fast);
     GNMS_CHECK_ARG(sym != 3 || fast, "launch_tail: the in-launch symmetry check needs the fast tail");
     int rc;
     GNMS_DISPATCH_SORT(P2, {
-        if ((rc = allow_lds(tail_kernel<E, BOXES>, lds))) return rc;
+        if ((rc = allow_lds(tail_kernel<E, SRC>, lds))) return rc;
         const int spw = leaders_chain_wgs(N, sym, chain_cap);
         // sym 3: symmetry checkers in front of the chain (one 16-wave workgroup per 128 pairs of 64 x 64 bit blocks: fewer, so that the chain workgroups behind them in the grid start sooner, at most the CUs the chain leaves)
         int nchk = 0;
         if (sym == 3) {
             const long nb = (N + 63) / 64, pairs = (long)B * nb * (nb + 1) / 2;
-            const int room = device_cu_count() - B * (spw + fast);
+            const int room = gnms_device_cu_count() - B * (spw + fast);
             nchk = (int)std::min<long>(std::max(room, 8), (pairs + 127) / 128);
             if (nchk < 1) nchk = 1;
         }
-        tail_kernel<E, BOXES><<<nchk + B * (spw + fast), 1024, lds, st>>>(src, N, (long)ld, counts, P, ws, L, P2, prob, (long long*)valid, (long long*)invalid, nvalid,
-                                                          ninvalid, sym, B, spw, fast, nchk);
+        tail_kernel<E, SRC><<<nchk + B * (spw + fast), 1024, lds, c.st>>>(src, N, (long)ld, c.counts, c.P, c.ws, c.L, P2, c.prob, (long long*)c.valid, (long long*)c.invalid,
+                                                                          c.nvalid, c.ninvalid, sym, B, spw, fast, nchk);
     });
     GNMS_CHECK_LAUNCH();
     return GNMS_OK;
@@ -1157,14 +1255,11 @@ bool sym_writers_in_tail_launch(int N, int64_t ld, const float* out) {
 
 // K3..K6 of every image + the matrix in one launch (tail_write_kernel)
 template <int SRC>
-int launch_tail_write(const float* chain_src, const float* write_src, int B, int N, const int32_t* counts, const gnms_params& P, char* ws,
-                      const gnms_ws_layout& L, float* prob, int64_t* valid, int64_t* invalid, int32_t* nvalid, int32_t* ninvalid, float* out,
-                      int64_t ld, hipStream_t st) {
-    int P2 = next_pow2(N);
-    if (P2 < 1024) P2 = 1024;
-    // (the fused K5 -> K6 hand-off, E <= 4, parks order[] and a copy of r2 behind the key region: 16 bytes per key)
-    const size_t llds = leaders_lds_bytes(N), glds = (size_t)P2 * (P2 <= 4096 ? 16 : 8);
-    size_t lds = llds > glds ? llds : glds;
+int launch_tail_write(const LayerCall& c, const float* chain_src, const float* write_src, float* out, int64_t ld) {
+    const int B = c.B, N = c.N;
+    const int P2 = c.P2 < 1024 ? 1024 : c.P2;
+    const int fast = (fast_tail_enabled() && fast_tail_ok(N, c.P, 1)) ? 1 : 0;
+    size_t lds = tail_lds_bytes(N, P2, fast);
     const int tr = kFusedTileRows;
     int staged = (SRC == kFromBoxes && N <= 4096) ? 1 : 0;           // writers_staged_2d: the image's boxes in LDS
     if (staged && lds < (size_t)N * 16) lds = (size_t)N * 16;
@@ -1174,9 +1269,7 @@ int launch_tail_write(const float* chain_src, const float* write_src, int B, int
         if (lds < 2 * gnms_iou3d::kSymTileBytes) lds = 2 * gnms_iou3d::kSymTileBytes;
         writers = (long)gnms_iou3d::sym_tiles_per_image(N) * B;
     }
-    const int fast = (fast_tail_enabled() && fast_tail_ok(N, P, 1)) ? 1 : 0;
-    if (fast && lds < fast_tail_lds_size(N, P2)) lds = fast_tail_lds_size(N, P2);
-    const int cus = device_cu_count();
+    const int cus = gnms_device_cu_count();
     if (writers > cus) writers = cus;
     // How many CUs write.  With the packed row body (iou_tile.h) a writer workgroup sustains ~29 GB/s and the stream saturates near
     // 5.8 TB/s from ~200 of them; more writers add nothing to the matrix and slow the chain beside them, whose loads queue behind
@@ -1192,12 +1285,12 @@ int launch_tail_write(const float* chain_src, const float* write_src, int B, int
     GNMS_DISPATCH_SORT(P2, {
         if (vec) {
             if ((rc = allow_lds(tail_write_kernel<true, E, SRC>, lds))) return rc;
-            gnms_launch_prof(kProfMatrixWrite, tail_write_kernel<true, E, SRC>, grid, dim3(1024), lds, st, chain_src, write_src, N, counts, P, ws,
-                             L, P2, prob, (long long*)valid, (long long*)invalid, nvalid, ninvalid, B, out, (long)ld, tr, 0, N, staged, fast);
+            gnms_launch_prof(kProfMatrixWrite, tail_write_kernel<true, E, SRC>, grid, dim3(1024), lds, c.st, chain_src, write_src, N, c.counts, c.P, c.ws,
+                             c.L, P2, c.prob, (long long*)c.valid, (long long*)c.invalid, c.nvalid, c.ninvalid, B, out, (long)ld, tr, 0, N, staged, fast);
         } else {
             if ((rc = allow_lds(tail_write_kernel<false, E, SRC>, lds))) return rc;
-            gnms_launch_prof(kProfMatrixWrite, tail_write_kernel<false, E, SRC>, grid, dim3(1024), lds, st, chain_src, write_src, N, counts, P,
-                             ws, L, P2, prob, (long long*)valid, (long long*)invalid, nvalid, ninvalid, B, out, (long)ld, tr, 0, N, staged, fast);
+            gnms_launch_prof(kProfMatrixWrite, tail_write_kernel<false, E, SRC>, grid, dim3(1024), lds, c.st, chain_src, write_src, N, c.counts, c.P,
+                             c.ws, c.L, P2, c.prob, (long long*)c.valid, (long long*)c.invalid, c.nvalid, c.ninvalid, B, out, (long)ld, tr, 0, N, staged, fast);
         }
     });
     GNMS_CHECK_LAUNCH();
@@ -1207,60 +1300,30 @@ int launch_tail_write(const float* chain_src, const float* write_src, int B, int
 // A small image's whole forward pass as ONE launch (nms_one_launch.h): masked groups, hard sort, N <= 1024 (one super-block), a 16-byte
 // aligned matrix with ld % 4 == 0, and no more workgroups than two rounds of the machine (every one asks for the chain's LDS, so a CU
 // holds one).  GNMS_ONE_LAUNCH=0: never (developer / test switch: the three-launch path stays reachable for A/B runs and the tests).
-bool one_launch_enabled() {
-    static const bool on = [] { const char* e = getenv("GNMS_ONE_LAUNCH"); return !(e && e[0] == '0'); }();
-    return on;
-}
-struct OneLaunchPlan { int kpw, split, grid; };
-bool one_launch_plan(int B, int N, const gnms_params& P, OneLaunchPlan* plan) {
-    if (!one_launch_enabled() || !fast_tail_enabled() || N > kOneLaunchMaxN || !fast_tail_ok(N, P, 1)) return false;
-    const int cus = device_cu_count();
-    const int NP = (N + 63) & ~63, NB = NP / 64;
-    const int kpw = (NP % 128 == 0 && (long)B * (NP / 32) <= (long)cus / 2) ? 32 : 64;
-    int split = 4;                                                // table workgroups: 16 rows each while that leaves the machine half empty
-    while (split > 1 && (long)B * NB * split > (long)cus / 2) split >>= 1;
-    const long grid = (long)B * (NP / kpw + NB * split + 2);
-    if (grid > 2L * cus) return false;
-    plan->kpw = kpw; plan->split = split; plan->grid = (int)grid;
-    return true;
-}
-int launch_one_matrix(const float* scores, const float* iou, int B, int N, int64_t ld, const int32_t* counts, const gnms_params& P, char* ws,
-                      const gnms_ws_layout& L, float* prob, int64_t* order, int64_t* valid, int64_t* invalid, int32_t* nvalid, int32_t* ninvalid,
-                      hipStream_t st, const OneLaunchPlan& plan) {
-    const size_t lds = one_launch_lds_size(N, false);
-    int rc;
-    if ((rc = allow_lds(one_launch_kernel<kFromMatrix>, lds))) return rc;
-    // (profile slot of the matrix READ: this launch holds the layer's one pass over the matrix -- bench.py's `roofline_matrix_in`)
-    gnms_launch_prof(kProfMatrixRead, one_launch_kernel<kFromMatrix>, dim3((unsigned)plan.grid), dim3(1024), lds, st, scores, iou, N, (long)ld, counts, P, ws, L, prob,
-                     (long long*)valid, (long long*)invalid, nvalid, ninvalid, (long long*)order, B, plan.kpw, plan.split);
-    GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
-}
-
+bool one_launch_enabled() { static const bool on = env_switch("GNMS_ONE_LAUNCH", 1) != 0; return on; }
+struct OneLaunchPlan { bool ok; int kpw, tpw, split; long front; };   // front: the launch's workgroups without the matrix writers
 // keys per sort workgroup with the x-order table: 64.  (Measured: 128 keys a workgroup -- two sort roles + the tables then fit one round of the
 // machine, so every table workgroup is resident from the start -- loses to the longer count: B = 8 N = 1024 31.0 against 29.7 us, B = 8 N = 768
 // 27.4 / 26.6, B = 4 N = 1024 30.3 / 29.1; 32 keys where that fits half the machine: B = 2 N = 1024 28.0 / 28.2 -- no difference.)
 constexpr int kXtKpw = 64;
-// which table the one-call entry's one launch builds: 0 none (three launches), 1 rank space (one 64 x 64 task per workgroup, while all tasks
-// are at most one round of the machine), 2 sources in x order (beyond that, while the launch's front is at most two rounds)
-int one_launch_boxes_mode(int B, int N) {
-    const int cus = device_cu_count();
+// The geometry of the one launch, for the layer from the matrix (gnms_forward: src = kFromMatrix) and for the one-call entry
+// (gnms_forward_with_iou2d: src = kFromBoxes), and whether the call takes it at all -- the pointers' alignment apart, which the launchers look at.
+OneLaunchPlan one_launch_plan(int src, int B, int N, const gnms_params& P) {
+    OneLaunchPlan p = {false, 0, 0, 0, 0};
+    if (!one_launch_enabled() || !fast_tail_enabled() || N > kOneLaunchMaxN || !fast_tail_ok(N, P, 1)) return p;
+    const int cus = gnms_device_cu_count();
     const int NP = (N + 63) & ~63, NB = NP / 64, nbp = NB * (NB + 1) / 2;
-    const int kpw = (NP % 128 == 0 && (long)B * (NP / 32) <= (long)cus / 2) ? 32 : 64;
-    if ((long)B * nbp <= (long)cus && nbp <= 13 * 32) return (long)B * (NP / kpw + nbp + 2) <= 3L * cus ? 1 : 0;
-    return (long)B * (2 * (NP / kXtKpw) + NB + 2) <= 2L * cus ? 2 : 0;
-}
-
-// the one-call entry (gnms_forward_with_iou2d, masked groups): the same with the table from the boxes and the matrix writers behind the chain
-int launch_one_boxes(const float* scores, const float* boxes, int B, int N, const int32_t* counts, const gnms_params& P, char* ws,
-                     const gnms_ws_layout& L, float* prob, int64_t* order, int64_t* valid, int64_t* invalid, int32_t* nvalid, int32_t* ninvalid,
-                     float* out, int64_t ld, hipStream_t st, bool* launched) {
-    *launched = false;
-    if (!one_launch_enabled() || !fast_tail_enabled() || N > kOneLaunchMaxN || !fast_tail_ok(N, P, 1) || B > kClaimImgs) return GNMS_OK;
-    if (!((ld % 4 == 0) && ((uintptr_t)out % 16 == 0))) return GNMS_OK;
-    const int cus = device_cu_count();
-    const int NP = (N + 63) & ~63, NB = NP / 64, nbp = NB * (NB + 1) / 2;
-    int kpw = (NP % 128 == 0 && (long)B * (NP / 32) <= (long)cus / 2) ? 32 : 64;
+    p.kpw = (NP % 128 == 0 && (long)B * (NP / 32) <= (long)cus / 2) ? 32 : 64;
+    if (src == kFromMatrix) {
+        p.split = 4;                                              // table workgroups: 16 rows each while that leaves the machine half empty
+        while (p.split > 1 && (long)B * NB * p.split > (long)cus / 2) p.split >>= 1;
+        p.front = (long)B * (NP / p.kpw + NB * p.split + 2);
+        p.ok = p.front <= 2L * cus;
+        return p;
+    }
+    if (B > kClaimImgs) return p;
+    // which table the one-call entry's one launch builds: rank space (tpw = 1: one 64 x 64 task per workgroup, while all tasks are at most one
+    // round of the machine), sources in x order (tpw = 0: beyond that, while the launch's front is at most two rounds), or none (three launches)
     // One task (a 64 x 64 block of pair decisions on 16 waves) per table workgroup, and only while all of them are about one round of the
     // machine: in rank space nothing can be culled, and where the tasks queue the three launches (x-sorted, culled bit matrix: 5-7 us) win.
     // Kernel time of the launch against sort + bits + tail_write_kernel, us (profiles/r06g_*): B = 8 N = 256 18.3 / 25.0, B = 16 N = 256
@@ -1272,15 +1335,45 @@ int launch_one_boxes(const float* scores, const float* boxes, int B, int N, cons
     // B = 4 N = 1024 29.8 / 32.0, B = 16 N = 512 24.1 / 29.0, B = 8 N = 768 27.6 / 32.5, B = 4 N = 768 25.8 / 27.3, B = 2 N = 1024 28.9 / 31.1,
     // B = 8 N = 512 24.4 / 25.9 -- and below a round of tasks the rank-space table wins: B = 1 N = 1024 27.1 / 25.0, B = 4 N = 512 23.2 / 20.2,
     // B = 16 N = 256 21.9 / 18.8, B = 8 N = 256 22.0 / 18.3, B = 1, 2 N = 500 21.8 / 19.4, 22.5 / 19.6.
-    const int mode = one_launch_boxes_mode(B, N);
-    if (mode == 0) return GNMS_OK;
-    const bool xt = mode == 2;
-    if (xt) kpw = kXtKpw;
-    const int tpw = xt ? 0 : 1;
-    const int ntab = nbp;
-    const long front = xt ? (long)B * (2 * (NP / kpw) + NB + 2) : (long)B * (NP / kpw + ntab + 2);
+    if ((long)B * nbp <= (long)cus && nbp <= 13 * 32) {
+        p.tpw = 1;
+        p.front = (long)B * (NP / p.kpw + nbp + 2);
+        p.ok = p.front <= 3L * cus;
+    } else {
+        p.kpw = kXtKpw;
+        p.tpw = 0;
+        p.front = (long)B * (2 * (NP / kXtKpw) + NB + 2);
+        p.ok = p.front <= 2L * cus;
+    }
+    return p;
+}
+// (both launchers: *launched stays false where the call does not take the one launch)
+int launch_one_matrix(const LayerCall& c, const float* scores, const float* iou, int64_t ld, bool* launched) {
+    *launched = false;
+    if (!((ld % 4 == 0) && ((uintptr_t)iou % 16 == 0))) return GNMS_OK;
+    const OneLaunchPlan plan = one_launch_plan(kFromMatrix, c.B, c.N, c.P);
+    if (!plan.ok) return GNMS_OK;
+    const size_t lds = one_launch_lds_size(c.N, false);
+    int rc;
+    if ((rc = allow_lds(one_launch_kernel<kFromMatrix>, lds))) return rc;
+    // (profile slot of the matrix READ: this launch holds the layer's one pass over the matrix -- bench.py's `roofline_matrix_in`)
+    gnms_launch_prof(kProfMatrixRead, one_launch_kernel<kFromMatrix>, dim3((unsigned)plan.front), dim3(1024), lds, c.st, scores, iou, c.N, (long)ld, c.counts, c.P, c.ws, c.L,
+                     c.prob, (long long*)c.valid, (long long*)c.invalid, c.nvalid, c.ninvalid, (long long*)c.order, c.B, plan.kpw, plan.split);
+    GNMS_CHECK_LAUNCH();
+    *launched = true;
+    return GNMS_OK;
+}
+
+// the one-call entry (gnms_forward_with_iou2d, masked groups): the same with the table from the boxes and the matrix writers behind the chain
+int launch_one_boxes(const LayerCall& c, const float* scores, const float* boxes, float* out, int64_t ld, bool* launched) {
+    *launched = false;
+    if (!((ld % 4 == 0) && ((uintptr_t)out % 16 == 0))) return GNMS_OK;
+    const OneLaunchPlan plan = one_launch_plan(kFromBoxes, c.B, c.N, c.P);
+    if (!plan.ok) return GNMS_OK;
+    const int B = c.B, N = c.N, cus = gnms_device_cu_count();
+    const bool xt = plan.tpw == 0;
     int* claims = nullptr;
-    int rc = claim_slot_for(st, &claims);
+    int rc = claim_slot_for(c.st, &claims);
     if (rc == kNoClaimSlot) return GNMS_OK;
     if (rc) return rc;
     const int ncc = (N + gnms_iou::kWaveCols - 1) / gnms_iou::kWaveCols, nrt = (N + kStagedRows - 1) / kStagedRows;
@@ -1293,84 +1386,49 @@ int launch_one_boxes(const float* scores, const float* boxes, int B, int N, cons
     size_t lds = one_launch_lds_size(N, true);
     if (lds < (size_t)N * 16) lds = (size_t)N * 16;
     if ((rc = allow_lds(one_launch_boxes_kernel, lds))) return rc;
-    gnms_launch_prof(kProfMatrixWrite, one_launch_boxes_kernel, dim3((unsigned)(front + writers)), dim3(1024), lds, st, scores, boxes, N, counts, P, ws, L, prob,
-                     (long long*)valid, (long long*)invalid, nvalid, ninvalid, (long long*)order, B, kpw, tpw, out, (long)ld, claims, (int)writers);
+    gnms_launch_prof(kProfMatrixWrite, one_launch_boxes_kernel, dim3((unsigned)(plan.front + writers)), dim3(1024), lds, c.st, scores, boxes, N, c.counts, c.P, c.ws, c.L,
+                     c.prob, (long long*)c.valid, (long long*)c.invalid, c.nvalid, c.ninvalid, (long long*)c.order, B, plan.kpw, plan.tpw, out, (long)ld, claims,
+                     (int)writers);
     GNMS_CHECK_LAUNCH();
     *launched = true;
     return GNMS_OK;
 }
 
-int forward_impl(const char* fn, const float* scores, const float* iou, int B, int N, int64_t ld, const int32_t* counts,
-                 const gnms_params* params, float* prob, int64_t* order, int64_t* valid, int64_t* invalid, int32_t* nvalid,
-                 int32_t* ninvalid, void* workspace, size_t workspace_bytes, void* stream, bool scores_already_sorted,
-                 const float* boxes2d = nullptr) {
-    // boxes2d: the 2D boxes `iou` was computed from (gnms_forward_with_iou2d), 16-byte aligned, or null: the ungrouped mode then builds
-    // its pruned lower-triangular matrix from them instead of reading `iou` back
-    int rc = check_common(fn, B, N, ld, params, workspace, workspace_bytes);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (B == 0) return GNMS_OK;
-    if (N == 0) {
-        if (nvalid) GNMS_CHECK_HIP(hipMemsetAsync(nvalid, 0, sizeof(int32_t) * B, st));
-        if (ninvalid) GNMS_CHECK_HIP(hipMemsetAsync(ninvalid, 0, sizeof(int32_t) * B, st));
-        return GNMS_OK;
-    }
-    GNMS_CHECK_ARG(scores && iou && prob, "gnms_forward: null scores/iou/prob");
-    const gnms_params P = *params;
-    const gnms_ws_layout L = gnms_make_layout(N);
-    char* ws = (char*)workspace;
-    const int P2 = next_pow2(N);
-    const size_t sort_lds = (size_t)P2 * 8;
-    const int sort_threads = P2 <= 1024 ? P2 : 1024;
-
-    {   // a small image: sort, threshold bits and chain as one launch
-        OneLaunchPlan plan;
-        if (!scores_already_sorted && (ld % 4 == 0) && ((uintptr_t)iou % 16 == 0) && one_launch_plan(B, N, P, &plan))
-            return launch_one_matrix(scores, iou, B, N, ld, counts, P, ws, L, prob, order, valid, invalid, nvalid, ninvalid, st, plan);
-    }
-    const bool permute_from_boxes = boxes2d && !P.group_boxes && !P.presorted && !scores_already_sorted;
+// the layer from the matrix.  boxes2d: the 2D boxes `iou` was computed from (gnms_forward_with_iou2d), 16-byte aligned, or null: the
+// ungrouped mode then builds its pruned lower-triangular matrix from them instead of reading `iou` back
+int forward_matrix(const LayerCall& c, const float* scores, const float* iou, int64_t ld, const float* boxes2d = nullptr) {
+    const int B = c.B, N = c.N;
+    const gnms_params& P = c.P;
+    int rc;
+    bool launched = false;                                        // a small image: sort, threshold bits and chain as one launch
+    if ((rc = launch_one_matrix(c, scores, iou, ld, &launched)) || launched) return rc;
+    const bool permute_from_boxes = boxes2d && !P.group_boxes && !P.presorted;
     // (with the boxes the score sort also leaves them in rank order, rbox; its second role, the boxes by x centre, is not used here)
-    if (!scores_already_sorted && (rc = launch_sorts(scores, permute_from_boxes ? boxes2d : nullptr, B, N, counts, ws, L, P2, order, st))) return rc;
+    if ((rc = launch_sorts(c, scores, permute_from_boxes ? boxes2d : nullptr))) return rc;
 
     if (P.group_boxes && P.mask_group_boxes && use_tail_kernel(N, matrix_sym_detection(N) ? 2 : 0)) {
         // (with the fast tail the symmetry check is a role of the tail launch and the scan runs on trust beside it: sym 3)
         const int sym = matrix_sym_detection(N) ? ((fast_tail_enabled() && fast_tail_ok(N, P, 2)) ? 3 : 2) : 0;
-        if ((rc = launch_bitmask(iou, B, N, ld, counts, P.nms_threshold, ws, L, st, sym == 3 ? 2 : (sym ? 1 : 0)))) return rc;
-        return launch_tail<false>(iou, B, N, ld, counts, P, ws, L, prob, valid, invalid, nvalid, ninvalid, st, sym);
+        if ((rc = launch_bitmask(c, iou, ld, sym == 3 ? 2 : (sym ? 1 : 0)))) return rc;
+        return launch_tail<kFromMatrix>(c, iou, ld, sym);
     }
     if (P.group_boxes) {
-        if ((rc = run_grouping(iou, B, N, ld, counts, P.nms_threshold, ws, L, st))) return rc;
-        GNMS_DISPATCH_SORT(P2, {
-            if ((rc = allow_lds(groups_kernel<E, false>, sort_lds))) return rc;
-            groups_kernel<E, false><<<B, sort_threads, sort_lds, st>>>(iou, N, (long)ld, counts, P, ws, L, P2);
-        });
-        GNMS_CHECK_LAUNCH();
-        if (!P.mask_group_boxes) {
-            const size_t lds = kSolveGroupsLds;
-            if ((rc = allow_lds(solve_groups_kernel<false, false>, lds))) return rc;
-            solve_groups_kernel<false, false><<<dim3(solve_groups_wgs(B, device_cu_count()), B), 1024, lds, st>>>(iou, N, (long)ld, counts, P, ws, L, nullptr, nullptr);
-            GNMS_CHECK_LAUNCH();
-        }
-    } else {
-        float* Ps = reinterpret_cast<float*>(ws + (size_t)B * L.per_image);      // scratch behind the per-image regions
-        const size_t plds = (size_t)N * 4;
-        if ((rc = allow_lds(ungrouped_permute_kernel, plds))) return rc;
-        ungrouped_prepare_kernel<<<dim3(gnms_div_up(N, 1024), B), 1024, 0, st>>>(N, counts, P, ws, L);
-        GNMS_CHECK_LAUNCH();
-        if (permute_from_boxes) ungrouped_permute_boxes_kernel<<<dim3(gnms_div_up(N, kPermuteRows), B), 256, 0, st>>>(N, counts, P, ws, L, Ps);
-        else ungrouped_permute_kernel<<<dim3(N, B), 256, plds, st>>>(iou, N, (long)ld, counts, P, ws, L, Ps);
-        GNMS_CHECK_LAUNCH();
-        if ((rc = allow_lds(ungrouped_solve_forward_kernel, kUngroupedFwdLds))) return rc;
-        ungrouped_solve_forward_kernel<<<dim3(gnms_div_up(N, kUB), B), kUThreads, kUngroupedFwdLds, st>>>(scores, N, counts, P, ws, L, Ps);
-        GNMS_CHECK_LAUNCH();
+        const int sym = matrix_sym_detection(N) ? 2 : 0;
+        if ((rc = launch_bitmask(c, iou, ld, sym ? 1 : 0))) return rc;
+        return launch_separate_tail<kFromMatrix>(c, iou, ld, sym);
     }
-    GNMS_DISPATCH_SORT(P2, {
-        if ((rc = allow_lds(finalize_kernel<E>, sort_lds))) return rc;
-        finalize_kernel<E><<<B, sort_threads, sort_lds, st>>>(N, counts, P, ws, L, P2, prob, (long long*)valid, (long long*)invalid,
-                                                               nvalid, ninvalid);
-    });
+    float* Ps = reinterpret_cast<float*>(c.ws + (size_t)B * c.L.per_image);      // scratch behind the per-image regions
+    const size_t plds = (size_t)N * 4;
+    if ((rc = allow_lds(ungrouped_permute_kernel, plds))) return rc;
+    ungrouped_prepare_kernel<<<dim3(gnms_div_up(N, 1024), B), 1024, 0, c.st>>>(N, c.counts, P, c.ws, c.L);
     GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
+    if (permute_from_boxes) ungrouped_permute_boxes_kernel<<<dim3(gnms_div_up(N, kPermuteRows), B), 256, 0, c.st>>>(N, c.counts, P, c.ws, c.L, Ps);
+    else ungrouped_permute_kernel<<<dim3(N, B), 256, plds, c.st>>>(iou, N, (long)ld, c.counts, P, c.ws, c.L, Ps);
+    GNMS_CHECK_LAUNCH();
+    if ((rc = allow_lds(ungrouped_solve_forward_kernel, kUngroupedFwdLds))) return rc;
+    ungrouped_solve_forward_kernel<<<dim3(gnms_div_up(N, kUB), B), kUThreads, kUngroupedFwdLds, c.st>>>(scores, N, c.counts, P, c.ws, c.L, Ps);
+    GNMS_CHECK_LAUNCH();
+    return launch_finalize(c);
 }
 
 }  // namespace
@@ -1378,8 +1436,10 @@ int forward_impl(const char* fn, const float* scores, const float* iou, int B, i
 extern "C" int gnms_forward(const float* scores, const float* iou, int B, int N, int64_t ld, const int32_t* counts,
                             const gnms_params* params, float* prob, int64_t* order, int64_t* valid, int64_t* invalid,
                             int32_t* nvalid, int32_t* ninvalid, void* workspace, size_t workspace_bytes, void* stream) {
-    return forward_impl("gnms_forward", scores, iou, B, N, ld, counts, params, prob, order, valid, invalid, nvalid, ninvalid, workspace,
-                        workspace_bytes, stream, false);
+    LayerCall c;
+    GNMS_BEGIN_CALL("gnms_forward", &c, B, N, ld, counts, params, workspace, workspace_bytes, stream, false, scores && iou && prob,
+                    "gnms_forward: null scores/iou/prob", prob, order, valid, invalid, nvalid, ninvalid);
+    return forward_matrix(c, scores, iou, ld);
 }
 
 namespace {
@@ -1456,31 +1516,33 @@ struct SideScope {
 }  // namespace
 
 namespace {
-int forward_boxes_impl(const float* boxes, const float* scores, int B, int N, const int32_t* counts, const gnms_params* params,
-                       float* prob, int64_t* order, int64_t* valid, int64_t* invalid, int32_t* nvalid, int32_t* ninvalid,
-                       void* workspace, size_t workspace_bytes, void* stream, bool scores_already_sorted, const MatrixWrite* mw = nullptr);
-}
+int forward_boxes(const LayerCall& c, const float* boxes, const float* scores, const MatrixWrite* mw = nullptr);
 
-namespace {
-// masked from-boxes layer: K3..K6 of every image and the matrix write as ONE launch (tail_write_kernel).
-bool chain_rides_in_write_launch(int B, int N) {
-    // (up to N = 1024 the score / x sorts could ride in the IoU launch instead, rounds 1-3's iou2d_sort_kernel; replayed as a HIP graph -- the GPU's
-    // own time -- this sequence measures the same or better there too: B = 8, N = 128 / 256 / 512 / 1024: 42.4 / 41.0 / 41.5 / 52.1 us
-    // against 38.0 / 36.6 / 40.0 / 47.5)
-    return true;
+// Where the 3D entry's matrix is written (masked hard-sorted groups): in_tail -- K3..K6 and the matrix in one launch (tail_write_kernel), like
+// the 2D entry; beside -- on the side stream; neither -- a launch of its own in front of the layer.
+struct Write3dRoute { bool in_tail, beside; };
+Write3dRoute write3d_route(int B, int N, int64_t ld, const float* out, float thr) {
+    const bool culled_bits = thr >= 0.01f && thr < INFINITY;         // the culled bit-matrix kernel writes full symmetric rows of W
+    // 1024 < N, no side stream: K3..K6 ride in the launch of the SYMMETRIC writers (tail_write_kernel, writers_sym_persistent) behind
+    // the from-records bit-matrix kernel
+    const bool sym_tail = culled_bits && sym_writers_in_tail_launch(N, ld, out);
+    const bool beside = !sym_tail && use_side_stream(B, N, ld);
+    // K3..K6 inside the write launch like the 2D entry -- up to N = 2048 only: the 3D writers are VALU-bound (23 slots per pair) and
+    // at the one workgroup per CU that launch runs at they lose more than the overlap buys (B = 8, N = 4096: launch 166 us against a
+    // 107-us write + 55-us chain, step 0.264 against 0.248 ms; N = 2048: 0.117 against 0.163 ms)
+    return Write3dRoute{!beside && culled_bits && (N <= 2048 || sym_tail), beside};
 }
 }  // namespace
 
 // name, as a kernel trace lists it, of the launch that writes the matrix inside gnms_forward_with_iou2d (dim 2) / _iou3d (dim 3)
-// (default parameters, aligned inputs)
+// (default parameters, aligned inputs): the entries' own route decisions, asked for such a call
 extern "C" const char* gnms_profile_write_kernel_name(int dim, int B, int N) {
     if (B <= 0 || N <= 0) return "";
-    if (dim == 3 && chain_rides_in_write_launch(B, N) && sym_writers_in_tail_launch(N, N, nullptr)) return "tail_write_kernel";
-    if (use_side_stream(B, N, N)) return dim == 3 ? "iou3d_nms_fast_kernel" : (N % 4 == 0 ? "write_staged_kernel" : "iou2d_kernel");
-    if (dim == 2 && N <= kOneLaunchMaxN && one_launch_enabled() && fast_tail_enabled() && one_launch_boxes_mode(B, N) != 0) return "one_launch_boxes_kernel";
-    if (chain_rides_in_write_launch(B, N) && (dim == 2 || N <= 2048)) return "tail_write_kernel";
-    if (dim == 3) return "iou3d_nms_fast_kernel";
-    return "iou2d_kernel";
+    gnms_params P;
+    gnms_default_params(&P);
+    if (dim == 3) return write3d_route(B, N, N, nullptr, P.nms_threshold).in_tail ? "tail_write_kernel" : "iou3d_nms_fast_kernel";
+    if (use_side_stream(B, N, N)) return N % 4 == 0 ? "write_staged_kernel" : "iou2d_kernel";
+    return one_launch_plan(kFromBoxes, B, N, P).ok ? "one_launch_boxes_kernel" : "tail_write_kernel";
 }
 
 // The matrix is an OUTPUT here, so the layer does not have to read it back: with the boxes at hand the grouped modes
@@ -1491,32 +1553,28 @@ extern "C" int gnms_forward_with_iou2d(const float* boxes, const float* scores, 
                                        const gnms_params* params, float* iou_out, float* prob, int64_t* order, int64_t* valid,
                                        int64_t* invalid, int32_t* nvalid, int32_t* ninvalid, void* workspace, size_t workspace_bytes,
                                        void* stream) {
-    int rc = check_common("gnms_forward_with_iou2d", B, N, ld, params, workspace, workspace_bytes);
-    if (rc) return rc;
-    if (B > 0 && N > 0) GNMS_CHECK_ARG(boxes && scores && iou_out && prob, "gnms_forward_with_iou2d: null pointer");
-    const bool from_boxes = params->group_boxes && !params->presorted && ((uintptr_t)boxes % 16 == 0);
-    const bool beside = B > 0 && N > 0 && from_boxes && params->mask_group_boxes && use_side_stream(B, N, ld);
+    LayerCall c;
+    GNMS_BEGIN_CALL("gnms_forward_with_iou2d", &c, B, N, ld, counts, params, workspace, workspace_bytes, stream, false,
+                    boxes && scores && iou_out && prob, "gnms_forward_with_iou2d: null pointer", prob, order, valid, invalid, nvalid, ninvalid);
+    const gnms_params& P = c.P;
+    const bool from_boxes = P.group_boxes && !P.presorted && ((uintptr_t)boxes % 16 == 0);
+    const bool beside = from_boxes && P.mask_group_boxes && use_side_stream(B, N, ld);
+    // masked from-boxes layer, no side stream: K3..K6 of every image and the matrix write as ONE launch (tail_write_kernel), always
+    // (up to N = 1024 the score / x sorts could ride in the IoU launch instead, rounds 1-3's iou2d_sort_kernel; replayed as a HIP graph -- the GPU's
+    // own time -- this sequence measures the same or better there too: B = 8, N = 128 / 256 / 512 / 1024: 42.4 / 41.0 / 41.5 / 52.1 us
+    // against 38.0 / 36.6 / 40.0 / 47.5)
     // (unmasked groups, round 4b: K3..K5's group structure rides in the write launch too, up to N = 4096; the per-group solves and K6 follow)
-    const bool chain_in_write = B > 0 && N > 0 && from_boxes && (params->mask_group_boxes || N <= 4096) && !beside && chain_rides_in_write_launch(B, N);
-    if (chain_in_write) {
-        const MatrixWrite mw = {iou_out, ld, true};
-        return forward_boxes_impl(boxes, scores, B, N, counts, params, prob, order, valid, invalid, nvalid, ninvalid, workspace,
-                                  workspace_bytes, stream, false, &mw);
-    }
-    if (beside) {
-        const MatrixWrite mw = {iou_out, ld, false};
-        return forward_boxes_impl(boxes, scores, B, N, counts, params, prob, order, valid, invalid, nvalid, ninvalid, workspace,
-                                  workspace_bytes, stream, false, &mw);
+    if (from_boxes && (P.mask_group_boxes || N <= 4096)) {
+        const MatrixWrite mw = {iou_out, ld, !beside};
+        return forward_boxes(c, boxes, scores, &mw);
     }
     // every other mode: the matrix by gnms_iou2d's own kernels (the persistent writers for a box set with itself), then the layer.
     // (Rounds 1-3 carried the score sort in the last grid slice of a 64 x 256-tile IoU launch here, iou2d_sort_kernel: 135 us at B = 8,
     // N = 4096 where the writers take 92 and the two sort launches 15; removed in round 4b.)
-    if (B > 0 && N > 0 && (rc = gnms_iou2d(boxes, boxes, B, N, N, iou_out, ld, stream))) return rc;
-    if (from_boxes)
-        return forward_boxes_impl(boxes, scores, B, N, counts, params, prob, order, valid, invalid, nvalid, ninvalid, workspace,
-                                  workspace_bytes, stream, false);
-    return forward_impl("gnms_forward_with_iou2d", scores, iou_out, B, N, ld, counts, params, prob, order, valid, invalid, nvalid,
-                        ninvalid, workspace, workspace_bytes, stream, false, ((uintptr_t)boxes % 16 == 0) ? boxes : nullptr);
+    int rc;
+    if ((rc = gnms_iou2d(boxes, boxes, B, N, N, iou_out, ld, stream))) return rc;
+    if (from_boxes) return forward_boxes(c, boxes, scores);
+    return forward_matrix(c, scores, iou_out, ld, ((uintptr_t)boxes % 16 == 0) ? boxes : nullptr);
 }
 
 // defined in iou_kernels.hip
@@ -1529,9 +1587,11 @@ namespace {
 // everything of gnms_forward_with_iou3d that uses the temporary `rec` ([B][N] records, then [B][N] pseudo boxes for the x sort).
 // Masked hard-sorted groups: the whole layer runs from the records (threshold bits AND the O(N) single overlaps, same arithmetic
 // as the matrix kernel), so nothing waits for the matrix; large images write it on the side stream beside the one-launch tail.
-int forward_with_iou3d_on(float* rec, const float* params3d, const float* scores, int B, int N, int64_t ld, const int32_t* counts,
-                          const gnms_params& P, float* iou_out, float* prob, int64_t* order, int64_t* valid, int64_t* invalid,
-                          int32_t* nvalid, int32_t* ninvalid, char* ws, const gnms_ws_layout& L, hipStream_t st) {
+int forward_with_iou3d_on(const LayerCall& c, float* rec, const float* params3d, const float* scores, int64_t ld, float* iou_out) {
+    const int B = c.B, N = c.N;
+    const gnms_params& P = c.P;
+    const gnms_ws_layout& L = c.L;
+    hipStream_t st = c.st;
     const bool from_rec = P.group_boxes && P.mask_group_boxes && !P.presorted;
     int rc;
     if (!from_rec) {
@@ -1539,24 +1599,16 @@ int forward_with_iou3d_on(float* rec, const float* params3d, const float* scores
         return gnms_internal_nms_overlap3d(rec, B, N, iou_out, ld, st, P.nms_threshold);
     }
     float* xkeys = rec + (size_t)B * N * gnms_iou3d::kRec;         // [B][N] pseudo boxes; later the rank-ordered records
-    if ((rc = gnms_internal_records_for_layer(params3d, B, N, rec, ws, L, xkeys, st))) return rc;
-    // 1024 < N, no side stream: K3..K6 ride in the launch of the SYMMETRIC writers (tail_write_kernel, writers_sym_persistent) behind
-    // the from-records bit-matrix kernel
-    const bool culled_bits = P.nms_threshold >= 0.01f && P.nms_threshold < INFINITY;
-    const bool sym_tail = culled_bits && chain_rides_in_write_launch(B, N) && sym_writers_in_tail_launch(N, ld, iou_out);
-    const bool beside = !sym_tail && use_side_stream(B, N, ld);
+    if ((rc = gnms_internal_records_for_layer(params3d, B, N, rec, c.ws, L, xkeys, st))) return rc;
+    const Write3dRoute route = write3d_route(B, N, ld, iou_out, P.nms_threshold);
+    const bool beside = route.beside, chain_in_write = route.in_tail;
     const int sym = (P.nms_threshold >= 0.01f && P.nms_threshold < INFINITY) ? 1 : 0;   // the culled kernel writes full symmetric rows of W
-    // K3..K6 inside the write launch like the 2D entry -- up to N = 2048 only: the 3D writers are VALU-bound (23 slots per pair) and
-    // at the one workgroup per CU that launch runs at they lose more than the overlap buys (B = 8, N = 4096: launch 166 us against a
-    // 107-us write + 55-us chain, step 0.264 against 0.248 ms; N = 2048: 0.117 against 0.163 ms)
-    const bool chain_in_write = !beside && sym && (N <= 2048 || sym_tail) && chain_rides_in_write_launch(B, N);
     if (!beside && !chain_in_write && (rc = gnms_internal_nms_overlap3d(rec, B, N, iou_out, ld, st, P.nms_threshold))) return rc;
-    const int P2 = next_pow2(N);
     // + the cuboids in the column order of the bit-matrix kernel: (z band, x centre).  Bands: so that a slot of 64 consecutive columns is
     // about as deep in z as it is wide in x (a handful of bands of >= 512 cuboids each; one band up to N = 1024)
     // (B = 8 uniform cuboids, bit-matrix kernel: N = 4096 52 / 47 / 46 / 46.5 us with 1 / 4 / 8 / 12 bands, N = 16384 494 / 409 / 407 with 1 / 8 / 15)
     const int bands = std::max(1, std::min(8, N / 512));
-    if ((rc = launch_sorts(scores, xkeys, B, N, counts, ws, L, P2, order, st, bands))) return rc;
+    if ((rc = launch_sorts(c, scores, xkeys, bands))) return rc;
     SideScope scope(st);
     // the part of the write that runs beside the bit-matrix kernel: rows [0, r1) of the all-pairs kernel
     const int r1 = beside ? split_rows(N, 20) : 0;
@@ -1567,7 +1619,7 @@ int forward_with_iou3d_on(float* rec, const float* params3d, const float* scores
     }
     if (!sym) {
         // no culling possible below that threshold: the triangular tile set does half the pairs of the square one
-        bitmask_rec3d_kernel<<<dim3(gnms_div_up(tri_tile_count(L.NB), 4), 1, B), 256, 0, st>>>(N, counts, P.nms_threshold, ws, L);
+        bitmask_rec3d_kernel<<<dim3(gnms_div_up(tri_tile_count(L.NB), 4), 1, B), 256, 0, st>>>(N, c.counts, P.nms_threshold, c.ws, L);
     } else {
         // row groups of 4 blocks where there are plenty of tiles; from N > 4096 the row groups are dealt to the XCDs (see the kernel)
         const long long tiles = (long long)B * L.NB * ((N + 255) / 256);
@@ -1576,41 +1628,22 @@ int forward_with_iou3d_on(float* rec, const float* params3d, const float* scores
         const int nkbg = gnms_div_up(L.NB, kbw), nchunk = (N + 255) / 256;
         const unsigned gx = pinned ? (unsigned)(gnms_div_up(nkbg, 8) * gnms_div_up(nchunk, 4) * 8) : (unsigned)gnms_div_up(nkbg * nchunk, 4);
         if (kbw >= 4)
-            bitmask_rec3d_culled_kernel<4><<<dim3(gx, 1, B), 256, 0, st>>>(N, counts, P.nms_threshold, ws, L, pinned);
+            bitmask_rec3d_culled_kernel<4><<<dim3(gx, 1, B), 256, 0, st>>>(N, c.counts, P.nms_threshold, c.ws, L, pinned);
         else
-            bitmask_rec3d_culled_kernel<1><<<dim3(gx, 1, B), 256, 0, st>>>(N, counts, P.nms_threshold, ws, L, pinned);
+            bitmask_rec3d_culled_kernel<1><<<dim3(gx, 1, B), 256, 0, st>>>(N, c.counts, P.nms_threshold, c.ws, L, pinned);
     }
     GNMS_CHECK_LAUNCH();
     if (chain_in_write)                                           // K3..K6 and the matrix in one launch, like the 2D entry
-        return launch_tail_write<kFromRecords>(nullptr, rec, B, N, counts, P, ws, L, prob, valid, invalid, nvalid, ninvalid, iou_out, ld, st);
-    if (beside) {                                                 // see forward_boxes_impl for why the fork sits exactly here
+        return launch_tail_write<kFromRecords>(c, nullptr, rec, iou_out, ld);
+    if (beside) {                                                 // see forward_boxes for why the fork sits exactly here
         hipStream_t side = nullptr;
         if ((rc = scope.fork(&side, 1))) return rc;
-        if ((rc = launch_tail<kFromRecords>(nullptr, B, N, ld, counts, P, ws, L, prob, valid, invalid, nvalid, ninvalid, st, sym, kBesideChainWGs))) return rc;
+        if ((rc = launch_tail<kFromRecords>(c, nullptr, ld, sym, kBesideChainWGs))) return rc;
         if ((rc = gnms_internal_nms_overlap3d(rec, B, N, iou_out, ld, side, P.nms_threshold, r1, N))) return rc;
         return scope.join();
     }
-    if (use_tail_kernel(N, sym)) return launch_tail<kFromRecords>(nullptr, B, N, ld, counts, P, ws, L, prob, valid, invalid, nvalid, ninvalid, st, sym);
-    const size_t llds = leaders_lds_bytes(N);
-    if ((rc = allow_lds(leaders_kernel, llds))) return rc;
-    { const int spw = leaders_chain_wgs(N, sym); leaders_kernel<<<B * spw, 1024, llds, st>>>(N, counts, ws, L, sym, B, spw); }
-    GNMS_CHECK_LAUNCH();
-    attribute_kernel<kFromRecords><<<dim3(L.NB, B), 64, 0, st>>>(nullptr, (long)ld, N, counts, P.nms_threshold, ws, L, sym);
-    GNMS_CHECK_LAUNCH();
-    const size_t sort_lds = (size_t)P2 * 8;
-    const int sort_threads = P2 <= 1024 ? P2 : 1024;
-    GNMS_DISPATCH_SORT(P2, {
-        if ((rc = allow_lds(groups_kernel<E, kFromRecords>, sort_lds))) return rc;
-        groups_kernel<E, kFromRecords><<<B, sort_threads, sort_lds, st>>>(nullptr, N, (long)ld, counts, P, ws, L, P2);
-    });
-    GNMS_CHECK_LAUNCH();
-    GNMS_DISPATCH_SORT(P2, {
-        if ((rc = allow_lds(finalize_kernel<E>, sort_lds))) return rc;
-        finalize_kernel<E><<<B, sort_threads, sort_lds, st>>>(N, counts, P, ws, L, P2, prob, (long long*)valid, (long long*)invalid, nvalid,
-                                                               ninvalid);
-    });
-    GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
+    if (use_tail_kernel(N, sym)) return launch_tail<kFromRecords>(c, nullptr, ld, sym);
+    return launch_separate_tail<kFromRecords>(c, nullptr, ld, sym);
 }
 }  // namespace
 
@@ -1622,41 +1655,32 @@ extern "C" int gnms_forward_with_iou3d(const float* params3d, const float* score
                                        const gnms_params* params, float* iou_out, float* prob, int64_t* order, int64_t* valid,
                                        int64_t* invalid, int32_t* nvalid, int32_t* ninvalid, void* workspace, size_t workspace_bytes,
                                        void* stream) {
-    int rc = check_common("gnms_forward_with_iou3d", B, N, ld, params, workspace, workspace_bytes);
-    if (rc) return rc;
-    if (B == 0 || N == 0)
-        return forward_impl("gnms_forward_with_iou3d", scores, iou_out, B, N, ld, counts, params, prob, order, valid, invalid, nvalid, ninvalid,
-                            workspace, workspace_bytes, stream, false);
-    GNMS_CHECK_ARG(params3d && scores && iou_out && prob, "gnms_forward_with_iou3d: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const gnms_params P = *params;
-    const gnms_ws_layout L = gnms_make_layout(N);
-    char* ws = (char*)workspace;
+    LayerCall c;
+    GNMS_BEGIN_CALL("gnms_forward_with_iou3d", &c, B, N, ld, counts, params, workspace, workspace_bytes, stream, false,
+                    params3d && scores && iou_out && prob, "gnms_forward_with_iou3d: null pointer", prob, order, valid, invalid, nvalid, ninvalid);
     // records of the whole batch in one stream-ordered temporary (the overlap kernel wants them contiguous); the layer's copy goes
     // into the per-image workspace regions
     float* rec = nullptr;
-    GNMS_CHECK_HIP(hipMallocAsync((void**)&rec, (size_t)B * N * (2 * gnms_iou3d::kRec) * sizeof(float), st));
-    rc = forward_with_iou3d_on(rec, params3d, scores, B, N, ld, counts, P, iou_out, prob, order, valid, invalid, nvalid, ninvalid, ws, L, st);
-    const hipError_t fe = hipFreeAsync(rec, st);                  // after the side stream, if any, has joined `st`
+    GNMS_CHECK_HIP(hipMallocAsync((void**)&rec, (size_t)B * N * (2 * gnms_iou3d::kRec) * sizeof(float), c.st));
+    const int rc = forward_with_iou3d_on(c, rec, params3d, scores, ld, iou_out);
+    const hipError_t fe = hipFreeAsync(rec, c.st);                // after the side stream, if any, has joined `st`
     if (rc) return rc;
     if (fe != hipSuccess) { gnms_set_error("hipFreeAsync failed: %s", hipGetErrorString(fe)); return GNMS_ERR_HIP; }
-    if (!(P.group_boxes && P.mask_group_boxes && !P.presorted))
-        return forward_impl("gnms_forward_with_iou3d", scores, iou_out, B, N, ld, counts, params, prob, order, valid, invalid, nvalid, ninvalid,
-                            workspace, workspace_bytes, stream, false);
+    if (!(c.P.group_boxes && c.P.mask_group_boxes && !c.P.presorted)) return forward_matrix(c, scores, iou_out, ld);
     return GNMS_OK;
 }
 
 extern "C" int gnms_backward(const float* grad_prob, const float* scores, const float* iou, int B, int N, int64_t ld,
                              const int32_t* counts, const gnms_params* params, float* grad_scores, float* grad_iou,
                              void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = check_common("gnms_backward", B, N, ld, params, workspace, workspace_bytes);
-    if (rc) return rc;
-    if (B == 0 || N == 0) return GNMS_OK;
-    GNMS_CHECK_ARG(grad_prob && scores && iou && grad_scores, "gnms_backward: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const gnms_params P = *params;
-    const gnms_ws_layout L = gnms_make_layout(N);
-    char* ws = (char*)workspace;
+    LayerCall c;
+    GNMS_BEGIN_CALL("gnms_backward", &c, B, N, ld, counts, params, workspace, workspace_bytes, stream, false,
+                    grad_prob && scores && iou && grad_scores, "gnms_backward: null pointer");
+    const gnms_params& P = c.P;
+    const gnms_ws_layout& L = c.L;
+    char* ws = c.ws;
+    hipStream_t st = c.st;
+    int rc;
     dim3 ge(gnms_div_up(N, 256), B);
     const bool fused_gx = P.group_boxes && P.mask_group_boxes && !P.return_sorted_prob && !P.presorted;   // the default path
     if (!fused_gx) {
@@ -1680,10 +1704,7 @@ extern "C" int gnms_backward(const float* grad_prob, const float* scores, const 
             GNMS_CHECK_LAUNCH();
         }
     } else if (P.group_boxes) {
-        const size_t lds = kSolveGroupsLds;
-        if ((rc = allow_lds(solve_groups_kernel<true, false>, lds))) return rc;
-        solve_groups_kernel<true, false><<<dim3(solve_groups_wgs(B, device_cu_count()), B), 1024, lds, st>>>(iou, N, (long)ld, counts, P, ws, L, grad_scores, grad_iou);
-        GNMS_CHECK_LAUNCH();
+        return launch_solve_groups<kBackward, kFromMatrix>(c, iou, ld, grad_scores, grad_iou);
     } else {
         const float* Ps = reinterpret_cast<const float*>(ws + (size_t)B * L.per_image);   // written by the forward pass
         ungrouped_backward_prepare_kernel<<<dim3(gnms_div_up(N, 1024), B), 1024, 0, st>>>(N, ws, L);
@@ -1703,30 +1724,11 @@ extern "C" int gnms_backward(const float* grad_prob, const float* scores, const 
 // from-boxes path: same layer, the N x N matrix never materialised (grouped modes)
 // ------------------------------------------------------------------------------------------------
 namespace {
-int forward_boxes_impl(const float* boxes, const float* scores, int B, int N, const int32_t* counts, const gnms_params* params,
-                       float* prob, int64_t* order, int64_t* valid, int64_t* invalid, int32_t* nvalid, int32_t* ninvalid,
-                       void* workspace, size_t workspace_bytes, void* stream, bool scores_already_sorted, const MatrixWrite* mw) {
-    int rc = check_common("gnms_forward_from_boxes", B, N, N, params, workspace, workspace_bytes);
-    if (rc) return rc;
-    if (!params->group_boxes || params->presorted) {
-        gnms_set_error("gnms_forward_from_boxes: only the grouped, hard-sorted modes run without the matrix");
-        return GNMS_ERR_UNSUPPORTED;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (B == 0) return GNMS_OK;
-    if (N == 0) {
-        if (nvalid) GNMS_CHECK_HIP(hipMemsetAsync(nvalid, 0, sizeof(int32_t) * B, st));
-        if (ninvalid) GNMS_CHECK_HIP(hipMemsetAsync(ninvalid, 0, sizeof(int32_t) * B, st));
-        return GNMS_OK;
-    }
-    GNMS_CHECK_ARG(boxes && scores && prob, "gnms_forward_from_boxes: null boxes/scores/prob");
-    GNMS_CHECK_ARG((uintptr_t)boxes % 16 == 0, "gnms_forward_from_boxes: boxes must be 16-byte aligned");
-    const gnms_params P = *params;
-    const gnms_ws_layout L = gnms_make_layout(N);
-    char* ws = (char*)workspace;
-    const int P2 = next_pow2(N);
-    const size_t sort_lds = (size_t)P2 * 8;
-    const int sort_threads = P2 <= 1024 ? P2 : 1024;
+int forward_boxes(const LayerCall& c, const float* boxes, const float* scores, const MatrixWrite* mw) {
+    const int B = c.B, N = c.N;
+    const gnms_params& P = c.P;
+    hipStream_t st = c.st;
+    int rc;
     // Large images: the matrix write is ONE persistent launch (write_staged_kernel) on the side stream that leaves B CUs without a
     // writer workgroup; forked behind the bit-matrix kernel, so that what runs beside it on the caller's stream is the one-workgroup-
     // per-image tail, which finds those CUs free (B = 8, N = 16384: write 1.60 ms = 5.4 TB/s, the tail 1.03 ms beside it, step 2.04 ms;
@@ -1734,37 +1736,28 @@ int forward_boxes_impl(const float* boxes, const float* scores, int B, int N, co
     // VALU-heavy kernels share the SIMDs and the sum stays the same (write 1.97 ms, step 2.01); forked in front of the sorts as well,
     // those crawl (step 2.35).
     const bool persistent_write = mw && !mw->one_launch && (mw->ld % 4 == 0) && ((uintptr_t)mw->out % 16 == 0) && (N % 4 == 0);
-    if (mw && mw->one_launch && !scores_already_sorted) {            // a small image: sort, table, chain and the matrix write as ONE launch
+    if (mw && mw->one_launch) {                                   // a small image: sort, table, chain and the matrix write as ONE launch
         bool launched = false;
-        if ((rc = launch_one_boxes(scores, boxes, B, N, counts, P, ws, L, prob, order, valid, invalid, nvalid, ninvalid, mw->out, mw->ld, st, &launched))) return rc;
-        if (launched) return GNMS_OK;
+        if ((rc = launch_one_boxes(c, scores, boxes, mw->out, mw->ld, &launched)) || launched) return rc;
     }
-    if (!scores_already_sorted && (rc = launch_sorts(scores, boxes, B, N, counts, ws, L, P2, order, st))) return rc;
+    if ((rc = launch_sorts(c, scores, boxes))) return rc;
     if (persistent_write) {
         SideScope whole(st);
         hipStream_t side = nullptr;
-        if ((rc = launch_bitmask_boxes(boxes, B, N, counts, P.nms_threshold, ws, L, st))) return rc;
+        if ((rc = launch_bitmask_boxes(c, boxes))) return rc;
         if ((rc = whole.fork(&side, 0))) return rc;
         // (the scan on at most kBesideChainWGs workgroups per image: their CUs are the ones the persistent write leaves free)
-        if ((rc = launch_tail<true>(boxes, B, N, N, counts, P, ws, L, prob, valid, invalid, nvalid, ninvalid, st, 1, kBesideChainWGs))) return rc;
+        if ((rc = launch_tail<kFromBoxes>(c, boxes, N, 1, kBesideChainWGs))) return rc;
         if ((rc = launch_write_staged(boxes, boxes, B, N, N, mw->out, mw->ld, B * leaders_chain_wgs(N, 1, kBesideChainWGs), side))) return rc;
         return whole.join();
     }
     if (mw && mw->one_launch) {
-        if ((rc = launch_bitmask_boxes(boxes, B, N, counts, P.nms_threshold, ws, L, st))) return rc;
-        if ((rc = launch_tail_write<kFromBoxes>(boxes, boxes, B, N, counts, P, ws, L, prob, valid, invalid, nvalid, ninvalid, mw->out, mw->ld, st))) return rc;
-        if (!P.mask_group_boxes) {                                    // unmasked groups: the chain stopped behind K5's group structure
-            const size_t lds = kSolveGroupsLds;
-            if ((rc = allow_lds(solve_groups_kernel<false, true>, lds))) return rc;
-            solve_groups_kernel<false, true><<<dim3(solve_groups_wgs(B, device_cu_count()), B), 1024, lds, st>>>(boxes, N, (long)N, counts, P, ws, L, nullptr, nullptr);
-            GNMS_CHECK_LAUNCH();
-            GNMS_DISPATCH_SORT(P2, {
-                if ((rc = allow_lds(finalize_kernel<E>, sort_lds))) return rc;
-                finalize_kernel<E><<<B, sort_threads, sort_lds, st>>>(N, counts, P, ws, L, P2, prob, (long long*)valid, (long long*)invalid, nvalid, ninvalid);
-            });
-            GNMS_CHECK_LAUNCH();
-        }
-        return GNMS_OK;
+        if ((rc = launch_bitmask_boxes(c, boxes))) return rc;
+        if ((rc = launch_tail_write<kFromBoxes>(c, boxes, boxes, mw->out, mw->ld))) return rc;
+        if (P.mask_group_boxes) return GNMS_OK;
+        // unmasked groups: the chain stopped behind K5's group structure
+        if ((rc = launch_solve_groups<kForward, kFromBoxes>(c, boxes, N, nullptr, nullptr))) return rc;
+        return launch_finalize(c);
     }
     SideScope beside(st);
     const int r1 = mw ? split_rows(N, 20) : 0;
@@ -1773,7 +1766,7 @@ int forward_boxes_impl(const float* boxes, const float* scores, int B, int N, co
         if ((rc = beside.fork(&side, 0))) return rc;
         if ((rc = gnms_internal_iou2d_rows(boxes, B, N, mw->out, mw->ld, side, 0, r1))) return rc;
     }
-    if ((rc = launch_bitmask_boxes(boxes, B, N, counts, P.nms_threshold, ws, L, st))) return rc;
+    if ((rc = launch_bitmask_boxes(c, boxes))) return rc;
     if (mw) {
         // Large images: the rest of the layer is one workgroup per image (K3..K6 in one launch) and the matrix write runs beside
         // it on the side stream.  The write is forked HERE and not earlier because its workgroups take every free wave slot: a
@@ -1782,70 +1775,37 @@ int forward_boxes_impl(const float* boxes, const float* scores, int B, int N, co
         // the event (same-queue successor ~2 us, cross-queue event ~25 us), and then keep their CUs until the layer is done.
         hipStream_t side = nullptr;
         if ((rc = beside.fork(&side, 1))) return rc;
-        if ((rc = launch_tail<true>(boxes, B, N, N, counts, P, ws, L, prob, valid, invalid, nvalid, ninvalid, st, 1, kBesideChainWGs))) return rc;
+        if ((rc = launch_tail<kFromBoxes>(c, boxes, N, 1, kBesideChainWGs))) return rc;
         if ((rc = gnms_internal_iou2d_rows(boxes, B, N, mw->out, mw->ld, side, r1, N))) return rc;
         return beside.join();
     }
-    if (P.mask_group_boxes && use_tail_kernel(N, 1))
-        return launch_tail<true>(boxes, B, N, N, counts, P, ws, L, prob, valid, invalid, nvalid, ninvalid, st, 1);
-    const size_t llds = leaders_lds_bytes(N);
-    if ((rc = allow_lds(leaders_kernel, llds))) return rc;
-    { const int spw = leaders_chain_wgs(N, 1); leaders_kernel<<<B * spw, 1024, llds, st>>>(N, counts, ws, L, 1, B, spw); }   // bitmask_boxes_kernel wrote full symmetric rows
-    GNMS_CHECK_LAUNCH();
-    attribute_kernel<true><<<dim3(L.NB, B), 64, 0, st>>>(boxes, (long)N, N, counts, P.nms_threshold, ws, L, 1);
-    GNMS_CHECK_LAUNCH();
-    GNMS_DISPATCH_SORT(P2, {
-        if ((rc = allow_lds(groups_kernel<E, true>, sort_lds))) return rc;
-        groups_kernel<E, true><<<B, sort_threads, sort_lds, st>>>(boxes, N, (long)N, counts, P, ws, L, P2);
-    });
-    GNMS_CHECK_LAUNCH();
-    if (!P.mask_group_boxes) {
-        const size_t lds = kSolveGroupsLds;
-        if ((rc = allow_lds(solve_groups_kernel<false, true>, lds))) return rc;
-        solve_groups_kernel<false, true><<<dim3(solve_groups_wgs(B, device_cu_count()), B), 1024, lds, st>>>(boxes, N, (long)N, counts, P, ws, L, nullptr, nullptr);
-        GNMS_CHECK_LAUNCH();
-    }
-    GNMS_DISPATCH_SORT(P2, {
-        if ((rc = allow_lds(finalize_kernel<E>, sort_lds))) return rc;
-        finalize_kernel<E><<<B, sort_threads, sort_lds, st>>>(N, counts, P, ws, L, P2, prob, (long long*)valid, (long long*)invalid,
-                                                               nvalid, ninvalid);
-    });
-    GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
+    // (sym 1: bitmask_boxes_kernel wrote full symmetric rows)
+    if (P.mask_group_boxes && use_tail_kernel(N, 1)) return launch_tail<kFromBoxes>(c, boxes, N, 1);
+    return launch_separate_tail<kFromBoxes>(c, boxes, N, 1);
 }
 }  // namespace
 
 extern "C" int gnms_forward_from_boxes(const float* boxes, const float* scores, int B, int N, const int32_t* counts,
                                        const gnms_params* params, float* prob, int64_t* order, int64_t* valid, int64_t* invalid,
                                        int32_t* nvalid, int32_t* ninvalid, void* workspace, size_t workspace_bytes, void* stream) {
-    return forward_boxes_impl(boxes, scores, B, N, counts, params, prob, order, valid, invalid, nvalid, ninvalid, workspace,
-                              workspace_bytes, stream, false);
+    LayerCall c;
+    GNMS_BEGIN_CALL("gnms_forward_from_boxes", &c, B, N, N, counts, params, workspace, workspace_bytes, stream, true, boxes && scores && prob,
+                    "gnms_forward_from_boxes: null boxes/scores/prob", prob, order, valid, invalid, nvalid, ninvalid);
+    GNMS_CHECK_ARG((uintptr_t)boxes % 16 == 0, "gnms_forward_from_boxes: boxes must be 16-byte aligned");
+    return forward_boxes(c, boxes, scores);
 }
 
 extern "C" int gnms_backward_from_boxes(const float* grad_prob, const float* boxes, const float* scores, int B, int N,
                                         const int32_t* counts, const gnms_params* params, float* grad_scores, void* workspace,
                                         size_t workspace_bytes, void* stream) {
-    int rc = check_common("gnms_backward_from_boxes", B, N, N, params, workspace, workspace_bytes);
-    if (rc) return rc;
-    if (!params->group_boxes || params->presorted) {
-        gnms_set_error("gnms_backward_from_boxes: only the grouped, hard-sorted modes run without the matrix");
-        return GNMS_ERR_UNSUPPORTED;
-    }
-    if (B == 0 || N == 0) return GNMS_OK;
-    GNMS_CHECK_ARG(grad_prob && boxes && scores && grad_scores, "gnms_backward_from_boxes: null pointer");
-    if (params->mask_group_boxes)      // the masked backward never touches the overlaps
+    LayerCall c;
+    GNMS_BEGIN_CALL("gnms_backward_from_boxes", &c, B, N, N, counts, params, workspace, workspace_bytes, stream, true,
+                    grad_prob && boxes && scores && grad_scores, "gnms_backward_from_boxes: null pointer");
+    if (c.P.mask_group_boxes)          // the masked backward never touches the overlaps
         return gnms_backward(grad_prob, scores, boxes, B, N, N, counts, params, grad_scores, nullptr, workspace, workspace_bytes, stream);
-    hipStream_t st = (hipStream_t)stream;
-    const gnms_params P = *params;
-    const gnms_ws_layout L = gnms_make_layout(N);
-    char* ws = (char*)workspace;
-    bwd_gx_kernel<<<dim3(gnms_div_up(N, 256), B), 256, 0, st>>>(grad_prob, N, counts, P, ws, L);
+    bwd_gx_kernel<<<dim3(gnms_div_up(N, 256), B), 256, 0, c.st>>>(grad_prob, N, counts, c.P, c.ws, c.L);
     GNMS_CHECK_LAUNCH();
-    const size_t lds = kSolveGroupsLds;
-    if ((rc = allow_lds(solve_groups_kernel<true, true>, lds))) return rc;
-    solve_groups_kernel<true, true><<<dim3(solve_groups_wgs(B, device_cu_count()), B), 1024, lds, st>>>(boxes, N, (long)N, counts, P, ws, L, grad_scores, nullptr);
-    GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
+    return launch_solve_groups<kBackward, kFromBoxes>(c, boxes, N, grad_scores, nullptr);
 }
 
 // Profiling hook: re-runs ONLY the threshold bit-matrix kernel (K2, the one full read of the matrix) on a
@@ -1857,8 +1817,8 @@ extern "C" int gnms_profile_bitmask(const float* iou, int B, int N, int64_t ld, 
     int rc = check_common("gnms_profile_bitmask", B, N, ld, &P, workspace, workspace_bytes);
     if (rc) return rc;
     if (B == 0 || N == 0) return GNMS_OK;
-    const gnms_ws_layout L = gnms_make_layout(N);
-    return launch_bitmask(iou, B, N, ld, counts, nms_threshold, (char*)workspace, L, (hipStream_t)stream);
+    P.nms_threshold = nms_threshold;
+    return launch_bitmask(make_call(B, N, counts, P, workspace, stream), iou, ld);
 }
 
 extern "C" int gnms_profile_bitmask_boxes(const float* boxes, int B, int N, const int32_t* counts, float nms_threshold, void* workspace,
@@ -1868,8 +1828,8 @@ extern "C" int gnms_profile_bitmask_boxes(const float* boxes, int B, int N, cons
     int rc = check_common("gnms_profile_bitmask_boxes", B, N, N, &P, workspace, workspace_bytes);
     if (rc) return rc;
     if (B == 0 || N == 0) return GNMS_OK;
-    const gnms_ws_layout L = gnms_make_layout(N);
-    return launch_bitmask_boxes(boxes, B, N, counts, nms_threshold, (char*)workspace, L, (hipStream_t)stream);
+    P.nms_threshold = nms_threshold;
+    return launch_bitmask_boxes(make_call(B, N, counts, P, workspace, stream), boxes);
 }
 
 // Profiling / test hook: ONLY the sorts (K1) of the 2D layer, on a chosen route, and what they leave in the workspace copied out.
@@ -1906,11 +1866,10 @@ extern "C" int gnms_profile_sorts(const float* scores, const float* boxes, int B
     GNMS_CHECK_ARG(route >= 0 && route <= 2, "gnms_profile_sorts: route %d (0 default, 1 runs + merge, 2 ranked runs)", route);
     if (B == 0 || N == 0) return GNMS_OK;
     GNMS_CHECK_ARG(scores != nullptr, "gnms_profile_sorts: scores is NULL");
-    const gnms_ws_layout L = gnms_make_layout(N);
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = launch_sorts(scores, boxes, B, N, counts, (char*)workspace, L, next_pow2(N), nullptr, st, 0, route))) return rc;
+    const LayerCall c = make_call(B, N, counts, P, workspace, stream);
+    if ((rc = launch_sorts(c, scores, boxes, 0, route))) return rc;
     if (order || rankof || sscore || rbox || xidx || xbox || flags) {
-        export_sorts_kernel<<<dim3(gnms_div_up(N, 256), B), 256, 0, st>>>(N, counts, (char*)workspace, L, boxes ? 1 : 0, order, rankof, sscore,
+        export_sorts_kernel<<<dim3(gnms_div_up(N, 256), B), 256, 0, c.st>>>(N, counts, c.ws, c.L, boxes ? 1 : 0, order, rankof, sscore,
                                                                           (float4*)rbox, xidx, (float4*)xbox, flags);
         GNMS_CHECK_LAUNCH();
     }
@@ -1955,23 +1914,18 @@ extern "C" int gnms_get_groups(const float* scores, const float* iou, int N, int
     GNMS_CHECK_ARG(ngroups_out != nullptr, "gnms_get_groups: ngroups_out is NULL");
     if (N == 0) { GNMS_CHECK_HIP(hipMemsetAsync(ngroups_out, 0, sizeof(int32_t), st)); return GNMS_OK; }
     GNMS_CHECK_ARG(scores && iou && group_of && pos_in_group, "gnms_get_groups: null pointer");
-    const gnms_ws_layout L = gnms_make_layout(N);
-    char* ws = (char*)workspace;
-    const int P2 = next_pow2(N);
-    const size_t sort_lds = (size_t)P2 * 8;
-    const int sort_threads = P2 <= 1024 ? P2 : 1024;
-    GNMS_DISPATCH_SORT(P2, {
-        if ((rc = allow_lds(sort_scores_kernel<E>, sort_lds))) return rc;
-        sort_scores_kernel<E><<<1, sort_threads, sort_lds, st>>>(scores, N, nullptr, ws, L, P2, nullptr, nullptr, 0);
+    const LayerCall c = make_call(1, N, nullptr, P, workspace, stream);
+    GNMS_DISPATCH_SORT(c.P2, {
+        if ((rc = allow_lds(sort_scores_kernel<E>, c.sort_lds()))) return rc;
+        sort_scores_kernel<E><<<1, c.sort_threads(), c.sort_lds(), st>>>(scores, N, nullptr, c.ws, c.L, c.P2, nullptr, nullptr, 0);
     });
     GNMS_CHECK_LAUNCH();
-    if ((rc = run_grouping(iou, 1, N, ld, nullptr, group_threshold, ws, L, st))) return rc;
-    GNMS_DISPATCH_SORT(P2, {
-        if ((rc = allow_lds(groups_kernel<E, false>, sort_lds))) return rc;
-        groups_kernel<E, false><<<1, sort_threads, sort_lds, st>>>(iou, N, (long)ld, nullptr, P, ws, L, P2);
-    });
-    GNMS_CHECK_LAUNCH();
-    export_groups_kernel<<<gnms_div_up(N, 256), 256, 0, st>>>(N, ws, L, group_of, pos_in_group, ngroups_out);
+    // grouping pipeline K2..K5, as the unmasked layer runs it
+    const int sym = matrix_sym_detection(N) ? 2 : 0;
+    if ((rc = launch_bitmask(c, iou, ld, sym ? 1 : 0))) return rc;
+    if ((rc = launch_leaders_attribute<kFromMatrix>(c, iou, ld, sym))) return rc;
+    if ((rc = launch_groups<kFromMatrix>(c, iou, ld))) return rc;
+    export_groups_kernel<<<gnms_div_up(N, 256), 256, 0, st>>>(N, c.ws, c.L, group_of, pos_in_group, ngroups_out);
     GNMS_CHECK_LAUNCH();
     return GNMS_OK;
 }

@@ -1171,6 +1171,53 @@ def test_iou2d_one_call_and_from_boxes_against_oracle_at_scale(G, O, B, N, kind)
             assert np.array_equal(s.grad[b].cpu().numpy(), ref["grad_scores"])
 
 
+def test_separate_launch_tail_from_boxes_against_oracle(G, O):
+    """gnms_forward_from_boxes, masked groups, ONE image of N = 4160 -- just past the fused tail's 4096, so K3..K6 run as launches of their
+    own from the boxes (leaders, attribution, groups, finalize) -- against the CPU oracle: probabilities, valid list, counts and score
+    gradient bit for bit, the invalid list as a set."""
+    from groomed_nms_amd import synthetic
+    N = 4160
+    boxes, scores = synthetic.batch_2d(57 + N, 1, N, "clustered")
+    w = np.linspace(-1, 2, N).astype(np.float32)
+    s = torch.from_numpy(scores).cuda().requires_grad_(True)
+    o = G.differentiable_nms_from_boxes_batched(s, torch.from_numpy(boxes).cuda())
+    (o[0] * torch.from_numpy(w).cuda()).sum().backward()
+    ref = O.differentiable_nms(scores[0], O.iou2d(boxes[0], boxes[0]), grad_prob=w)
+    nv, ni = int(o[4][0]), int(o[5][0])
+    assert np.array_equal(o[0][0].detach().cpu().numpy(), ref["prob"])
+    assert nv == len(ref["valid"]) and ni == len(ref["invalid"])
+    assert o[2][0, :nv].tolist() == list(ref["valid"])
+    assert sorted(o[3][0, :ni].tolist()) == sorted(ref["invalid"].tolist())
+    assert np.array_equal(s.grad[0].cpu().numpy(), ref["grad_scores"])
+
+
+def test_separate_launch_tail_from_records_against_oracle(G, O):
+    """gnms_forward_with_iou3d, masked groups, ONE image of N = 2112 at a threshold below the cull's 0.01 limit (0.005): the unculled
+    bit-matrix kernel writes no symmetric rows, so past N = 2048 K3..K6 run as launches of their own from the records.  The written matrix
+    against the oracle's exact operation order (within 2e-6, the same `> thr` decisions); and the layer against the oracle ON that matrix:
+    probabilities, valid list, counts and score gradient bit for bit, the invalid list as a set (the layer decides every pair as the
+    written entry does, and the masked linear mode has no transcendental)."""
+    from groomed_nms_amd import synthetic, overlaps
+    N, thr = 2112, 0.005
+    par, scores = synthetic.batch_3d(31 + N, 1, N, clustered=True, per=64)
+    pt = torch.from_numpy(par).cuda()
+    w = np.linspace(-1, 2, N).astype(np.float32)
+    s = torch.from_numpy(scores).cuda().requires_grad_(True)
+    o = G.differentiable_nms_with_iou3d_batched(s, pt, nms_threshold=thr)
+    (o[0] * torch.from_numpy(w).cuda()).sum().backward()
+    got = o[6][0].cpu().numpy()
+    c = overlaps.get_corners_of_cuboid(*[pt[0, :, i].contiguous() for i in range(7)]).cpu().numpy()
+    exact = _oracle_overlap3d(O, c)
+    assert float(np.abs(got - exact).max()) <= 2e-6 and np.array_equal(got > np.float32(thr), exact > np.float32(thr))
+    ref = O.differentiable_nms(scores[0], got, grad_prob=w, nms_threshold=thr)
+    nv, ni = int(o[4][0]), int(o[5][0])
+    assert np.array_equal(o[0][0].detach().cpu().numpy(), ref["prob"])
+    assert nv == len(ref["valid"]) and ni == len(ref["invalid"])
+    assert o[2][0, :nv].tolist() == list(ref["valid"])
+    assert sorted(o[3][0, :ni].tolist()) == sorted(ref["invalid"].tolist())
+    assert np.array_equal(s.grad[0].cpu().numpy(), ref["grad_scores"])
+
+
 def test_large_images_take_the_same_decisions(G):
     """B=8, N=8192 crosses every size switch at once: cooperative sorts (8 runs per image), 4 rank blocks per bit-matrix wave,
     separate K3..K6 launches.  One-call entry, matrix-free entry and matrix-in entry must agree bit for bit."""
