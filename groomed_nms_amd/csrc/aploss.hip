@@ -16,7 +16,7 @@
 //   6. grad[positives] = -(1 - prec)/F, grad[negatives] = grad_j/F, loss = 1 - mean(prec)  (:70-78)
 // delta is 1.0 whatever the caller asks for, as in the reference (:16).
 #include <cstdlib>
-#include "nms_kernels.h"
+#include "gnms_device.h"
 
 namespace {
 

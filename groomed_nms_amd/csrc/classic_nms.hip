@@ -14,7 +14,7 @@
 #include <mutex>
 #include <vector>
 #include <string.h>
-#include "nms_kernels.h"
+#include "nms_scan_kernels.h"
 
 namespace {
 
@@ -99,10 +99,9 @@ __global__ __launch_bounds__(256) void classic_mask_kernel(const float* __restri
     unsigned lo[J], hi[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) lo[j] = hi[j] = 0u;
-    // (round 6) the decision without the division where that is safe, as bitmask_boxes_body takes it: with d = fma(-thresh, uni, inter) (one
-    // rounding, sign exact) and uni > 0, |d| > guard * uni puts the exact quotient more than 8 ulp of the threshold's magnitude away from it, so
-    // its fp32 rounding lies on the same side and `ov > thresh` is `d > 0`; a row with a pair inside the band (or uni <= 0, NaN, inf) divides.
-    const float guard = fmaxf(fabsf(thresh), 1.0f) * 9.6e-7f;
+    // (round 6) the decision without the division where that is safe, as bitmask_boxes_body takes it (iou_guard_band, gnms_device.h): outside
+    // the band around d = fma(-thresh, uni, inter) = 0 `ov > thresh` is `d > 0`; a row with a pair inside the band (or uni <= 0, NaN, inf) divides.
+    const float guard = iou_guard_band(thresh);
 #pragma unroll 8
     for (int r = 0; r < 64; ++r) {
         const float ax1 = bcastf(rx1, r), ay1 = bcastf(ry1, r), ax2 = bcastf(rx2, r), ay2 = bcastf(ry2, r), as = bcastf(rs, r);
@@ -227,7 +226,7 @@ __global__ __launch_bounds__(1024) void classic_ext_kernel(const float* __restri
     const float* q = boxes + (size_t)(base + (k < m ? k : m - 1)) * dim;
     const float bx1 = q[0], by1 = q[1], bx2 = q[2], by2 = q[3];
     const float bs = (bx2 - bx1 + shift) * (by2 - by1 + shift);
-    const float guard = fmaxf(fabsf(thresh), 1.0f) * 9.6e-7f;          // (classic_mask_kernel's band: the two kernels take the same decisions)
+    const float guard = iou_guard_band(thresh);                        // (classic_mask_kernel's band: the two kernels take the same decisions)
     if (tid == 0) s_bits = 0ull;
     bool sup = false;
     for (int t0 = 0; t0 < nk; t0 += 1024) {

@@ -16,845 +16,31 @@
 //   K4 attribute     first-remover per box, parallel over rank blocks
 //   K5 groups        membership (strict >), cap, head, CSR of groups; default rescoring fused
 //   K6 finalize      clamp / threshold / second sort / valid + invalid lists / output order
+//
+// This is the LAYER's header (nms_layer.hip, through nms_backward_kernels.h / nms_solve_kernels.h / nms_one_launch.h).  What the rest of
+// the library borrows is in the three headers below: gnms_device.h (device primitives, no kernel), nms_sort_kernels.h (K1) and
+// nms_scan_kernels.h (K3).  A header that more than one .hip file includes defines no non-template __global__ function that one of
+// its includers does not launch (the build treats an unused one as an error): K2, K2s, K4..K6 and the tails stay here.
 #pragma once
 #include <type_traits>
-#include "gnms_common.h"
-#include "iou3d_pair.h"
+#include "gnms_device.h"
+#include "nms_sort_kernels.h"
+#include "nms_scan_kernels.h"
 #include "iou_tile.h"
 
 namespace gnms {
 namespace {   // internal linkage: the header is included by several translation units
 
-typedef unsigned long long u64;
-
-// Data that one workgroup of a launch hands to another workgroup of the SAME launch (the leader scan's granules and rem[], everything in
-// one_launch_kernel): the L2s of the eight XCDs are not coherent with each other inside a kernel, so such data leaves through agent-scope
-// (write-through) stores and is read with agent-scope loads.
-template <typename T> __device__ __forceinline__ T coh_load(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename T> __device__ __forceinline__ void coh_store(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float4 coh_load_f4(const float4* p) {
-    const u64 a = coh_load(reinterpret_cast<const u64*>(p)), c = coh_load(reinterpret_cast<const u64*>(p) + 1);
-    return make_float4(__uint_as_float((unsigned)a), __uint_as_float((unsigned)(a >> 32)), __uint_as_float((unsigned)c), __uint_as_float((unsigned)(c >> 32)));
-}
-__device__ __forceinline__ void coh_store_f4(float4* p, const float4 v) {
-    coh_store(reinterpret_cast<u64*>(p), ((u64)__float_as_uint(v.y) << 32) | __float_as_uint(v.x));
-    coh_store(reinterpret_cast<u64*>(p) + 1, ((u64)__float_as_uint(v.w) << 32) | __float_as_uint(v.z));
-}
-
-// ------------------------------------------------------------------------------------------------
-// Workgroup sort of P = blockDim.x * E 64-bit keys (P a power of two, blockDim.x a multiple of 64),
-// ascending.  Thread t owns elements t*E .. t*E+E-1 in registers.  A bitonic network whose stages run
-//   j <  E      in registers (compile-time partner),
-//   j <  64*E   as wave shuffles (partner lane = lane ^ j/E),
-//   j >= 64*E   through LDS (transposed [e][t] layout: conflict-free), two barriers each.
-// For P = 4096 that is 10 LDS stages instead of the 78 barrier-separated stages of a plain LDS bitonic.
-// On return the sorted keys are in r[] AND in keys[0..P) (natural order), barrier included.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 shfl_xor_key(u64 v, int m) {
-    const unsigned lo = __shfl_xor((unsigned)(v & 0xffffffffu), m, 64);
-    const unsigned hi = __shfl_xor((unsigned)(v >> 32), m, 64);
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned shfl_xor_key(unsigned v, int m) { return __shfl_xor(v, m, 64); }
-__device__ __forceinline__ u64 shfl_up_u64(u64 v, int off) {
-    const unsigned lo = __shfl_up((unsigned)(v & 0xffffffffu), off, 64);
-    const unsigned hi = __shfl_up((unsigned)(v >> 32), off, 64);
-    return ((u64)hi << 32) | lo;
-}
-
-#ifdef GNMS_TIMING
-__device__ long long g_sort_ticks[4];
-#define GNMS_ST0() long long st__ = (long long)__builtin_amdgcn_s_memtime()
-#define GNMS_STACC(slot) do { long long n__ = (long long)__builtin_amdgcn_s_memtime(); if (threadIdx.x == 0 && blockIdx.x == 0) g_sort_ticks[slot] += n__ - st__; st__ = n__; } while (0)
-#else
-#define GNMS_ST0() do {} while (0)
-#define GNMS_STACC(slot) do {} while (0)
-#endif
-
-template <int E, typename K>
-__device__ __forceinline__ void block_sort_bitonic(K (&r)[E], K* keys, int P) {
-    const int t = threadIdx.x;
-    const int T = blockDim.x;
-    GNMS_ST0();
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j >= 64 * E; j >>= 1) {                    // cross-wave stages
-#pragma unroll
-            for (int e = 0; e < E; ++e) keys[e * T + t] = r[e];
-            __syncthreads();
-            const int pt = t ^ (j / E);
-            const bool keepmin = (((t * E) & k) == 0) == (((t * E) & j) == 0);   // j >= E: the same for all E elements
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const K o = keys[e * T + pt];
-                r[e] = ((o < r[e]) == keepmin) ? o : r[e];              // one compare per exchange
-            }
-            __syncthreads();
-        }
-        GNMS_STACC(0);
-        {
-            int j = (k >> 1) < 64 * E ? (k >> 1) : 32 * E;              // intra-wave stages
-            for (; j >= E; j >>= 1) {
-                const int m = j / E;
-                const bool keepmin = (((t * E) & k) == 0) == (((t * E) & j) == 0);   // j >= E: the same for all E elements
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const K o = shfl_xor_key(r[e], m);
-                    r[e] = ((o < r[e]) == keepmin) ? o : r[e];
-                }
-            }
-        }
-        GNMS_STACC(1);
-#pragma unroll
-        for (int jj = E / 2; jj >= 1; jj >>= 1) {                        // in-register stages
-            if (jj < k) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    if ((e & jj) == 0) {
-                        const int i = t * E + e;
-                        const bool up = (i & k) == 0;
-                        const K a = r[e], b = r[e | jj];
-                        if ((a > b) == up) { r[e] = b; r[e | jj] = a; }
-                    }
-                }
-            }
-        }
-        GNMS_STACC(2);
-    }
-#pragma unroll
-    for (int e = 0; e < E; ++e) keys[t * E + e] = r[e];
-    __syncthreads();
-    GNMS_STACC(3);
-}
-
-// ------------------------------------------------------------------------------------------------
-// block_sort: the production sort.  Same contract as block_sort_bitonic (thread t owns t*E..t*E+E-1, result in
-// r[] and keys[0..P)), different cross-wave phase:
-//   1. every wave sorts its own 64*E keys ascending with the register/shuffle part of the bitonic network;
-//   2. the 64E-key runs are merged pairwise, log2(#waves) passes: each thread finds its E outputs by a merge-path
-//      binary search on the two runs in LDS and merges them sequentially (ties take the left run).
-// That replaces the 10 two-barrier LDS exchange stages + 24 shuffle stages above 64E of the pure bitonic network by
-// 4 passes for 4096 keys (measured: 25 -> ~14 us for u64 keys on one CU).
-// ------------------------------------------------------------------------------------------------
-template <int E, typename K>
-__device__ __forceinline__ void block_sort(K (&r)[E], K* keys, int P) {
-    const int t = threadIdx.x;
-    const int run = 64 * E < P ? 64 * E : P;                            // keys per wave-sorted run
-    // ---- phase 1: wave-local bitonic sort (all runs ascending: the direction bit is dropped at k == run) ----
-    for (int k = 2; k <= run; k <<= 1) {
-        const int kd = (k == run) ? 0 : k;
-        for (int j = k >> 1; j >= E; j >>= 1) {
-            const int m = j / E;
-            const bool keepmin = (((t * E) & kd) == 0) == (((t * E) & j) == 0);
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const K o = shfl_xor_key(r[e], m);
-                r[e] = ((o < r[e]) == keepmin) ? o : r[e];
-            }
-        }
-#pragma unroll
-        for (int jj = E / 2; jj >= 1; jj >>= 1) {
-            if (jj < k) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    if ((e & jj) == 0) {
-                        const int i = t * E + e;
-                        const bool up = (i & kd) == 0;
-                        const K a = r[e], b = r[e | jj];
-                        if ((a > b) == up) { r[e] = b; r[e | jj] = a; }
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < E; ++e) keys[t * E + e] = r[e];
-    __syncthreads();
-    // ---- phase 2: pairwise merge passes ----
-    for (int p = run; p < P; p <<= 1) {
-        const int d0 = t * E;
-        if (d0 >= P) { __syncthreads(); __syncthreads(); continue; }      // P < blockDim.x * E: the surplus threads only keep the barriers
-        const int base = d0 & ~(2 * p - 1);
-        const int d = d0 - base;                                        // diagonal inside the pair [A | B], |A| = |B| = p
-        const K* A = keys + base;
-        const K* Bk = keys + base + p;
-        int lo = d > p ? d - p : 0, hi = d < p ? d : p;
-        while (lo < hi) {                                               // merge path: first a with A[a] > B[d-1-a]
-            const int mid = (lo + hi) >> 1;
-            if (A[mid] <= Bk[d - 1 - mid]) lo = mid + 1; else hi = mid;
-        }
-        int a = lo, b = d - lo;
-        K ka = a < p ? A[a] : K(0), kb = b < p ? Bk[b] : K(0);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const bool takeA = (b >= p) || (a < p && ka <= kb);
-            r[e] = takeA ? ka : kb;
-            if (takeA) { ++a; ka = a < p ? A[a] : K(0); } else { ++b; kb = b < p ? Bk[b] : K(0); }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < E; ++e) keys[t * E + e] = r[e];
-        __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Stable LSD radix pass over P = blockDim.x * E 32-bit keys in LDS, 7 bits per pass (128 digits), in place.
-// Element order is the LDS order; wave w owns the 64*E consecutive slots [w*64E, (w+1)*64E), lane l reads slots e*64 + l
-// (conflict-free), so a round e covers 64 consecutive elements and the stable rank inside the wave is
-//   (same-digit elements of earlier rounds, kept in a per-wave histogram) + popcount(same-digit lanes below me),
-// the same-digit lane mask coming from 7 ballots.  A (digit-major, wave-minor) exclusive scan of the 128 x #waves histogram
-// gives every (wave, digit) its base.  5 barriers per pass; 2 passes sort 14-bit keys (the groups' leader ranks), where the
-// merge-path block_sort needs ~15 us for 4096 keys and this needs ~4.
-// hist: 128 * (blockDim.x / 64) + 16 unsigned words of LDS.
-// ------------------------------------------------------------------------------------------------
-template <int E>
-__device__ __forceinline__ void block_radix_pass7(unsigned* keys, int shift, unsigned* hist) {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nw = blockDim.x >> 6;
-    unsigned* wtot = hist + 128 * nw;
-    for (int i = t; i < 128 * nw; i += blockDim.x) hist[i] = 0u;
-    unsigned k[E], rnk[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) k[e] = keys[wave * 64 * E + e * 64 + lane];
-    __syncthreads();
-    const u64 below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const unsigned d = (k[e] >> shift) & 127u;
-        u64 same = ~0ull;
-#pragma unroll
-        for (int bit = 0; bit < 7; ++bit) {
-            const bool on = (d >> bit) & 1u;
-            const u64 bl = __ballot(on);
-            same &= on ? bl : ~bl;
-        }
-        const unsigned prior = hist[wave * 128 + d];
-        rnk[e] = prior + (unsigned)__builtin_popcountll(same & below);
-        if ((same & below) == 0ull) hist[wave * 128 + d] = prior + (unsigned)__builtin_popcountll(same);   // the digit's lowest lane
-        __builtin_amdgcn_wave_barrier();                                // the next round reads what this one wrote (same wave: in order)
-    }
-    __syncthreads();
-    // exclusive scan in (digit, wave) order: entry j = d * nw + w lives at hist[w * 128 + d]; thread t owns j = 2t, 2t + 1
-    const int j0 = 2 * t, j1 = 2 * t + 1;
-    const int lw = 31 - __builtin_clz(nw);                               // #waves is a power of two
-    const int a0 = (j0 & (nw - 1)) * 128 + (j0 >> lw), a1 = (j1 & (nw - 1)) * 128 + (j1 >> lw);
-    const unsigned c0 = hist[a0], c1 = hist[a1];
-    const unsigned inc = gnms_add_scan32(c0 + c1);                       // DPP prefix sum: no ds_bpermute round trips
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    // sum of the totals of the waves before mine (<= 16 of them): lane w < wave holds total w, lane 63 of the scan has the sum
-    const unsigned carry = (unsigned)__builtin_amdgcn_readlane((int)gnms_add_scan32((lane < wave) ? wtot[lane] : 0u), 63);
-    const unsigned ex = carry + inc - (c0 + c1);
-    hist[a0] = ex;
-    hist[a1] = ex + c0;
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < E; ++e) keys[hist[wave * 128 + ((k[e] >> shift) & 127u)] + rnk[e]] = k[e];
-    __syncthreads();
-}
-
-template <typename K>
-__device__ __forceinline__ int lower_bound_lds(const K* keys, int n, K v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (keys[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-struct ImgPtrs {
-    int* order; float* sscore; int* rankof; int* rem; int* head; int* gpos; int* gsorted; int* gstart; int* glen; int* hlist;
-    float* plead; float* pre; float* r2; int* sidx; float* xsol; float* gx; int* leadc; int* leadr; u64* leadw; int* leadpfx;
-    int* misc; u64* gran; int* xidx; float4* xbox; float4* rbox; float* rec; float* xrec; u64* W;
-};
-
-__device__ __host__ __forceinline__ ImgPtrs img_ptrs(char* ws, const gnms_ws_layout& L, int b) {
-    char* p = ws + (size_t)b * L.per_image;
-    ImgPtrs I;
-    I.order = (int*)(p + L.off_order); I.sscore = (float*)(p + L.off_sscore); I.rankof = (int*)(p + L.off_rankof); I.rem = (int*)(p + L.off_rem);
-    I.head = (int*)(p + L.off_head); I.gpos = (int*)(p + L.off_gpos); I.gsorted = (int*)(p + L.off_gsorted);
-    I.gstart = (int*)(p + L.off_gstart); I.glen = (int*)(p + L.off_glen); I.hlist = (int*)(p + L.off_hlist); I.plead = (float*)(p + L.off_plead);
-    I.pre = (float*)(p + L.off_pre); I.r2 = (float*)(p + L.off_r2); I.sidx = (int*)(p + L.off_sidx);
-    I.xsol = (float*)(p + L.off_xsol); I.gx = (float*)(p + L.off_gx); I.leadc = (int*)(p + L.off_leadc); I.leadr = (int*)(p + L.off_leadr);
-    I.leadw = (u64*)(p + L.off_leadw); I.leadpfx = (int*)(p + L.off_leadpfx); I.misc = (int*)(p + L.off_misc);
-    I.gran = (u64*)(p + L.off_gran); I.xidx = (int*)(p + L.off_xidx); I.xbox = (float4*)(p + L.off_xbox); I.rbox = (float4*)(p + L.off_rbox); I.rec = (float*)(p + L.off_rec); I.xrec = (float*)(p + L.off_xrec);
-    I.W = (u64*)(p + L.off_W);
-    return I;
-}
-
-// IoU of box a (row) against box b (column): the arithmetic of iou2d_kernel / lib/core.py:210-218,499-508, operation
-// for operation, so that the from-boxes path takes exactly the decisions the matrix path takes.
-__device__ __forceinline__ float pair_iou(const float4 a, const float4 b) {
-    const float area_a = (a.z - a.x) * (a.w - a.y);
-    const float area_b = (b.z - b.x) * (b.w - b.y);
-    const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.0f);
-    const float h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.0f);
-    const float inter = w * h;
-    return inter / ((area_a + area_b) - inter);
-}
-
-// Where the kernels that need single overlap entries take them from.  The template parameter is an int so that the existing
-// <false> / <true> instantiations keep meaning "matrix" / "2D boxes".
-constexpr int kFromMatrix = 0;     // src = the N x N matrix of the image, leading dimension ld
-constexpr int kFromBoxes = 1;      // src = the image's boxes [N][4]: lib/core.py iou recomputed (pair_iou, the arithmetic of iou2d_tile)
-constexpr int kFromRecords = 2;    // src = the image's corner-AABB records [N][12]: 0.5 * (1 + GIoU3D) recomputed (iou3d_pair.h)
-
-// element [ca][cb] (input indices)
-// thr: the layer's nms_threshold (records only: entries inside the guard band around it take the reference's exact order, iou3d_pair.h)
-template <int SRC>
-__device__ __forceinline__ float overlap_at(const float* __restrict__ src, long ld, int ca, int cb, float thr) {
-    if (SRC == kFromBoxes) {
-        const float4* bx = reinterpret_cast<const float4*>(src);
-        return pair_iou(bx[ca], bx[cb]);
-    }
-    if (SRC == kFromRecords) return gnms_iou3d::nms_overlap3d_pair(src + (size_t)ca * gnms_iou3d::kRec, src + (size_t)cb * gnms_iou3d::kRec, thr);
-    return src[(size_t)ca * ld + cb];
-}
-
-// the image's slice of what the caller passed as `src` (records live in the workspace, not in a caller array)
-template <int SRC>
-__device__ __forceinline__ const float* overlap_src(const float* __restrict__ src, const ImgPtrs& I, int b, int N, long ld) {
-    if (SRC == kFromRecords) return I.rec;
-    return src + (SRC == kFromBoxes ? (size_t)b * N * 4 : (size_t)b * N * ld);
-}
-
-// ------------------------------------------------------------------------------------------------
-// K1: stable descending argsort of the scores (lib/groomed_nms.py:41; get_groups :213)
-// ------------------------------------------------------------------------------------------------
-// Second, independent sort of the from-boxes path: the boxes by ascending x centre (NaN last).  bitmask_boxes_kernel walks
-// its COLUMNS in this order, so that the 256 columns of a wave tile are spatial neighbours and the rows that cannot touch
-// their hull are skipped.  Thread t owns elements t*E .. t*E+E-1; `keys` = P 64-bit LDS slots.
-// A box the packed intersection of bitmask_boxes_body may see: finite coordinates, no negative zero, x2 >= x1, y2 >= y1
-__device__ __forceinline__ bool box_orders_plainly(const float4 v) {
-    auto fine = [](float c) { const unsigned u = __float_as_uint(c); return u != 0x80000000u && (u & 0x7fffffffu) < 0x7f800000u; };
-    return fine(v.x) && fine(v.y) && fine(v.z) && fine(v.w) && v.z >= v.x && v.w >= v.y;
-}
-
-// Column order of the 3D bit-matrix kernel (bitmask_rec3d_slots_kernel): the cuboids arrive as pseudo boxes (x0, lx, x1, z0 + z1) and
-// are ordered by (z band, x centre) -- `mode3d` equal-width bands over the image's range of z0 + z1 -- so that 64 consecutive columns
-// (one SLOT of a wave tile) are a compact patch in x AND z and the rows far from it in either direction are skipped.  mode3d = 0: plain
-// 2D boxes by x centre; 1: cuboids, one band.  Key = band << 60 | x key << 28 | input index (N <= 16384): distinct, NaN x last.
-constexpr unsigned kColIdxMask = 0x0fffffffu;
-__device__ __forceinline__ u64 column_key(const float4 v, int i, int nbands, float zlo, float zscale) {
-    unsigned band = 0u;
-    if (nbands > 1) {
-        const float f = (v.w - zlo) * zscale;
-        band = (f == f) ? (unsigned)fminf(fmaxf(f, 0.0f), (float)(nbands - 1)) : (unsigned)(nbands - 1);
-    }
-    return ((u64)band << 60) | ((u64)(~gnms_desc_key(v.x + v.z)) << 28) | (unsigned)i;
-}
-// range of z0 + z1 over the image's finite pseudo boxes -> (zlo, nbands / (zhi - zlo)); every thread of the workgroup returns the same pair
-// (min / max do not depend on the order), so every workgroup of an image bands alike
-__device__ __forceinline__ void block_z_bands(const float4* __restrict__ bx, int n, int nbands, float* zlo_out, float* zscale_out) {
-    __shared__ float zred[2][16];
-    float lo = INFINITY, hi = -INFINITY;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float z = bx[i].w;
-        if (fabsf(z) < INFINITY) { lo = fminf(lo, z); hi = fmaxf(hi, z); }
-    }
-    lo = gnms_wave_min_f(lo); hi = gnms_wave_max_f(hi);
-    const int wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    if ((threadIdx.x & 63) == 0) { zred[0][wave] = lo; zred[1][wave] = hi; }
-    __syncthreads();
-    lo = INFINITY; hi = -INFINITY;
-    for (int w = 0; w < nw; ++w) { lo = fminf(lo, zred[0][w]); hi = fmaxf(hi, zred[1][w]); }
-    const float span = hi - lo;
-    *zlo_out = lo;
-    *zscale_out = (span > 0.0f && span < INFINITY) ? (float)nbands / span : 0.0f;
-    __syncthreads();
-}
-// what the column sort leaves behind for rank `k` of its order: the input index, the (pseudo) box, and for cuboids the record
-__device__ __forceinline__ void column_store(const ImgPtrs& I, int k, int idx, const float4 v, int mode3d) {
-    I.xidx[k] = idx;
-    I.xbox[k] = v;
-    if (mode3d) {
-        const float4* s = reinterpret_cast<const float4*>(I.rec) + (size_t)idx * 3;
-        float4* d = reinterpret_cast<float4*>(I.xrec) + (size_t)k * 3;
-        d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
-    }
-}
-
-template <int E>
-__device__ __forceinline__ void sort_boxes_by_x(const float* __restrict__ boxes, int n, const ImgPtrs& I, u64* keys, int P, int mode3d = 0) {
-    const float4* bx = reinterpret_cast<const float4*>(boxes);
-    float zlo = 0.0f, zscale = 0.0f;
-    if (mode3d > 1) block_z_bands(bx, n, mode3d, &zlo, &zscale);
-    u64 r[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = threadIdx.x * E + e;
-        r[e] = ~0ull;
-        if (i < n) r[e] = column_key(bx[i], i, mode3d, zlo, zscale);
-    }
-    block_sort<E, u64>(r, keys, P);
-    bool plain = true;
-    for (int k = threadIdx.x; k < n; k += blockDim.x) {
-        const int idx = (int)((unsigned)keys[k] & kColIdxMask);
-        const float4 v = bx[idx];
-        column_store(I, k, idx, v, mode3d);
-        plain = plain && box_orders_plainly(v);
-    }
-    const int all_plain = __syncthreads_and(plain);
-    if (threadIdx.x == 0) I.misc[6] = all_plain ? 0 : 1;              // bitmask_boxes_body: the packed intersection needs plain boxes
-}
-
-template <int E>
-__global__ __launch_bounds__(1024) void sort_scores_kernel(const float* __restrict__ scores, int N, const int* __restrict__ counts,
-                                                           char* ws, gnms_ws_layout L, int P, long long* __restrict__ order_out,
-                                                           const float* __restrict__ boxes, int mode3d) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* keys = reinterpret_cast<u64*>(smem);
-    const int b = blockIdx.x;
-    const int n = gnms_count(counts, b, N);
-    const float* s = scores + (size_t)b * N;
-    ImgPtrs I = img_ptrs(ws, L, b);
-    if (blockIdx.y == 1) {                      // from-boxes path only: grid (B, 2)
-        sort_boxes_by_x<E>(boxes + (size_t)b * N * 4, n, I, keys, P, mode3d);
-        return;
-    }
-    u64 r[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = threadIdx.x * E + e;
-        r[e] = (i < n) ? (((u64)gnms_desc_key(s[i]) << 32) | (unsigned)i) : ~0ull;
-    }
-    block_sort<E, u64>(r, keys, P);
-    int same = 1;
-    for (int k = threadIdx.x; k < N; k += blockDim.x) {
-        int idx = k;                  // padding ranks map to themselves
-        float v = 0.0f;
-        if (k < n) { idx = (int)(keys[k] & 0xffffffffu); v = s[idx]; }
-        same &= (idx == k);
-        I.order[k] = idx;
-        I.rankof[idx] = k;            // order is a permutation of [0,N) (identity on the padding)
-        I.sscore[k] = v;
-        if (boxes && k < n) I.rbox[k] = reinterpret_cast<const float4*>(boxes)[(size_t)b * N + idx];   // (the from-boxes layer: row boxes of the bit matrix)
-        if (order_out) order_out[(size_t)b * N + k] = idx;
-    }
-    // misc[2] = 1 when the scores came in already sorted (both reference call sites do that: lib/loss/rpn_3d.py:731-737,
-    // lib/rpn_util.py:1258-1266): rank == input index, so the bit-matrix kernel can skip the half of the matrix that no
-    // leader can reach and needs no scatter.
-    const int all_same = __syncthreads_and(same);
-    if (threadIdx.x < 8 && !(boxes && threadIdx.x == 6)) I.misc[threadIdx.x] = (threadIdx.x == 2) ? all_same : 0;   // ([6]: the x sort's)
-    if (threadIdx.x == 8) I.misc[8] = gnms_next_epoch(I.misc[8]);                   // the workspace's call counter (leaders_sb_body's hand-off tag)
-    for (int i = threadIdx.x; i < 17 * 32; i += blockDim.x) I.gran[i] = 0ull;   // (and no granule of this workspace carries a tag yet)
-}
-
-// ------------------------------------------------------------------------------------------------
-// K1 as runs + merge: the same two sorts (scores descending; boxes by x centre) spread over R = P/1024 workgroups per image.  The route of
-// N > 4096; up to 2048 keys the counting sort further down took over in round 5, and 2048 < N <= 4096 the ranked runs behind these two in
-// round 8 (launch_sorts in nms_layer.hip has the table; GNMS_RANK_SORT=0 brings that range back here).
-//   sort_runs_kernel  every workgroup sorts one run of 1024 keys in LDS (block_sort<1>) and parks it in global scratch
-//                      (the bit-matrix region W: nothing lives there before K2);
-//   sort_merge_kernel  every workgroup loads ALL runs of its image into LDS and ranks its own 1024 keys: final position =
-//                      own position + sum over the other runs of (number of keys below mine), R-1 branch-free binary searches
-//                      that advance in lock step (their LDS reads overlap).  Keys are distinct (index in the low word).
-// One workgroup per image needs 23 us at N=4096 and 103 us at N=16384 on its single CU; this needs about 10 / 20 us.
-// role (blockIdx.z): 0 = scores, 1 = boxes by x centre (from-boxes path).
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 sort_key_of(int role, const float* __restrict__ scores_img, const float* __restrict__ boxes_img, int i,
-                                           int nbands, float zlo, float zscale) {
-    if (role == 0) return ((u64)gnms_desc_key(scores_img[i]) << 32) | (unsigned)i;
-    return column_key(reinterpret_cast<const float4*>(boxes_img)[i], i, nbands, zlo, zscale);
-}
-
-// (run r of image b, role)
-__device__ __forceinline__ void sort_runs_body(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
-                                               const int* __restrict__ counts, char* ws, gnms_ws_layout L, int P, const int r, const int b,
-                                               const int role, const int mode3d = 0) {
-    __shared__ u64 keys[1024];
-    const int n = gnms_count(counts, b, N);
-    ImgPtrs I = img_ptrs(ws, L, b);
-    const int i = r * 1024 + (int)threadIdx.x;
-    float zlo = 0.0f, zscale = 0.0f;
-    if (role == 1 && mode3d > 1) block_z_bands(reinterpret_cast<const float4*>(boxes + (size_t)b * N * 4), n, mode3d, &zlo, &zscale);
-    u64 k[1];
-    k[0] = (i < n) ? sort_key_of(role, scores + (size_t)b * N, boxes ? boxes + (size_t)b * N * 4 : nullptr, i, mode3d, zlo, zscale) : ~0ull;
-    block_sort<1, u64>(k, keys, 1024);
-    I.W[(size_t)role * P + i] = k[0];
-    if (r == 0 && role == 0 && threadIdx.x < 8) I.misc[threadIdx.x] = (threadIdx.x == 2) ? 1 : 0;   // [2] = "already sorted", cleared below
-    if (r == 0 && role == 0 && threadIdx.x == 8) I.misc[8] = gnms_next_epoch(I.misc[8]);   // the workspace's call counter (leaders_sb_body's hand-off tag)
-    if (r == 0 && role == 0 && threadIdx.x < 17 * 32) I.gran[threadIdx.x] = 0ull;   // (and no granule of this workspace carries a tag yet)
-}
-
+// K1's two non-template kernels (bodies and their description: nms_sort_kernels.h)
 __global__ __launch_bounds__(1024) void sort_runs_kernel(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
                                                          const int* __restrict__ counts, char* ws, gnms_ws_layout L, int P, int mode3d) {
     sort_runs_body(scores, boxes, N, counts, ws, L, P, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, mode3d);
-}
-
-template <int R>
-__device__ __forceinline__ void sort_merge_body(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
-                                                const int* __restrict__ counts, char* ws, gnms_ws_layout L, long long* __restrict__ order_out,
-                                                const int r, const int b, const int role, const int mode3d = 0) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* all = reinterpret_cast<u64*>(smem);                          // [R][1024]
-    const int n = gnms_count(counts, b, N);
-    ImgPtrs I = img_ptrs(ws, L, b);
-    const int t = threadIdx.x;
-    const u64* runs = I.W + (size_t)role * (R * 1024);
-#pragma unroll
-    for (int q = 0; q < R; ++q)
-        all[q * 1024 + t] = runs[q * 1024 + t];
-    __syncthreads();
-    const u64 mine = all[r * 1024 + t];
-    int same = 1;
-    if (mine != ~0ull) {
-        // what leaves with the key -- its score, its box -- is fetched by INPUT index, known before the searches: requested here, the round
-        // trip runs under them (round 6: behind the rank it was one more exposed memory latency at the end of every workgroup)
-        const int idx = (int)((unsigned)mine & (role == 0 ? 0xffffffffu : kColIdxMask));
-        float sv = 0.0f;
-        float4 bv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (role == 0) sv = scores[(size_t)b * N + idx];
-        if (boxes) bv = reinterpret_cast<const float4*>(boxes)[(size_t)b * N + idx];
-        int pos[R];
-#pragma unroll
-        for (int q = 0; q < R; ++q) pos[q] = 0;
-#pragma unroll
-        for (int h = 512; h >= 1; h >>= 1) {
-#pragma unroll
-            for (int q = 0; q < R; ++q) pos[q] += (all[q * 1024 + pos[q] + h - 1] < mine) ? h : 0;
-        }
-        int rank = 0;
-#pragma unroll
-        for (int q = 0; q < R; ++q) rank += (q == r) ? t : pos[q] + ((all[q * 1024 + pos[q]] < mine) ? 1 : 0);
-        if (role == 0) {
-            same = (idx == rank);
-            I.order[rank] = idx;
-            I.rankof[idx] = rank;
-            I.sscore[rank] = sv;
-            if (boxes) I.rbox[rank] = bv;                             // (the from-boxes layer: row boxes of the bit matrix)
-            if (order_out) order_out[(size_t)b * N + rank] = idx;
-        } else {
-            column_store(I, rank, idx, bv, mode3d);
-            same = box_orders_plainly(bv);                            // (role 1: "every box of this run is plain")
-        }
-    }
-    if (role == 1 && !__syncthreads_and(same) && t == 0) I.misc[6] = 1;   // (zeroed by sort_runs_body, a launch earlier; every writer stores 1)
-    if (role == 0) {
-        // padding ranks map to themselves (order is a permutation of [0, N))
-        for (int k = n + r * 1024 + t; k < N; k += R * 1024) {
-            I.order[k] = k; I.rankof[k] = k; I.sscore[k] = 0.0f;
-            if (order_out) order_out[(size_t)b * N + k] = k;
-        }
-        if (!__syncthreads_and(same) && t == 0) I.misc[2] = 0;        // (every writer stores 0)
-    }
-}
-
-template <int R>
-__global__ __launch_bounds__(1024) void sort_merge_kernel(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
-                                                          const int* __restrict__ counts, char* ws, gnms_ws_layout L,
-                                                          long long* __restrict__ order_out, int mode3d) {
-    sort_merge_body<R>(scores, boxes, N, counts, ws, L, order_out, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, mode3d);
-}
-
-// ------------------------------------------------------------------------------------------------
-// K1 for 2048 < N <= 4096 (round 8): runs AND ranks in ONE launch, no workgroup waiting for another.  Runs + merge cost 8.1 + 6.4 us and a
-// launch boundary at B = 8 on 64 workgroups each, the keys going through HBM scratch in between.  Here workgroup (r, image, role) of
-// 16 builds ALL 4096 keys of its image and role (thread t: keys 4t .. 4t+3), each of its 16 waves sorts its own 256 keys in registers
-// (phase 1 of block_sort<4>: no barrier inside), the 16 sorted runs go into LDS, and the workgroup ranks the 256 keys of run r against all
-// runs: thread (key, quarter) searches the four runs of its quarter in lock step, the four partial counts meet in LDS.  Every image's
-// run sort is repeated 16 times -- on CUs that stood idle -- and that is what removes the second launch, the scratch and every hand-off.
-// 16 * B * roles workgroups: 256 at B = 8 with boxes; taken while that is one round of the machine (launch_sorts).  The flags are decided by workgroup 0 of each role alone, on the keys it holds
-// (as sort_count_body does): no flag depends on an earlier launch.
-// ------------------------------------------------------------------------------------------------
-constexpr int kRankRuns = 16;            // waves per workgroup = runs per image = workgroups per image and role
-constexpr int kRankRunKeys = 256;        // keys per run (E = 4 per lane)
-
-// lane ^ m of a 32-bit value, m a compile-time constant after unrolling: DPP where one exists (quad_perm for 1 and 2, row_ror:8 for 8, the two
-// halves of 4 as row_ror:12 into banks 0, 2 and row_ror:4 into banks 1, 3), ds_bpermute for 16 and 32.  18 of the run sort's 21 shuffle stages
-// are DPP that way; with ds_bpermute for all of them the launch took 14.6 us instead of 11.5 at B = 8 (LABNOTES R8.2)
-__device__ __forceinline__ unsigned xor_lanes32(unsigned v, int m) {
-    switch (m) {
-        case 1: return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);    // quad_perm:[1,0,3,2]
-        case 2: return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);    // quad_perm:[2,3,0,1]
-        case 4: {
-            const int a = __builtin_amdgcn_update_dpp(0, (int)v, 0x12C, 0xF, 0x5, false);         // row_ror:12 = lane + 4 -> lanes with bit 2 clear
-            return (unsigned)__builtin_amdgcn_update_dpp(a, (int)v, 0x124, 0xF, 0xA, false);      // row_ror:4  = lane - 4 -> lanes with bit 2 set
-        }
-        case 8: return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true);   // row_ror:8
-        default: break;
-    }
-    return __shfl_xor(v, m, 64);
-}
-__device__ __forceinline__ u64 xor_lanes(u64 v, int m) {
-    return ((u64)xor_lanes32((unsigned)(v >> 32), m) << 32) | xor_lanes32((unsigned)(v & 0xffffffffu), m);
-}
-
-// every wave sorts the 256 keys of its lanes' r[0..3] ascending (lane l ends with positions 4l .. 4l+3 of the run): the network of
-// block_sort's phase 1 for E = 4, fully unrolled so that every shuffle distance is a constant
-__device__ __forceinline__ void wave_sort_256(u64 (&r)[4]) {
-    const int i0 = ((int)threadIdx.x & 63) * 4;
-#pragma unroll
-    for (int k = 2; k <= kRankRunKeys; k <<= 1) {
-        const int kd = (k == kRankRunKeys) ? 0 : k;
-#pragma unroll
-        for (int j = k >> 1; j >= 4; j >>= 1) {
-            const bool keepmin = ((i0 & kd) == 0) == ((i0 & j) == 0);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const u64 o = xor_lanes(r[e], j / 4);
-                r[e] = ((o < r[e]) == keepmin) ? o : r[e];
-            }
-        }
-#pragma unroll
-        for (int jj = 2; jj >= 1; jj >>= 1) {
-            if (jj < k) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if ((e & jj) == 0) {
-                        const bool up = ((i0 + e) & kd) == 0;
-                        const u64 a = r[e], b = r[e | jj];
-                        if ((a > b) == up) { r[e] = b; r[e | jj] = a; }
-                    }
-                }
-            }
-        }
-    }
-}
-
-// (workgroup r of 16 of image b, role): grid (16, B, roles), 1024 threads, 4096 * 8 bytes of dynamic LDS; 2048 < N <= 4096
-__device__ __forceinline__ void sort_ranked_runs_body(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
-                                                      const int* __restrict__ counts, char* ws, gnms_ws_layout L,
-                                                      long long* __restrict__ order_out, const int r, const int b, const int role,
-                                                      const int mode3d = 0) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* keys = reinterpret_cast<u64*>(smem);                          // [16][256]: the image as 16 sorted runs (padding ~0: behind everything)
-    __shared__ int part[3][kRankRunKeys];                              // partial counts of quarters 1 .. 3
-    const int n = gnms_count(counts, b, N);
-    ImgPtrs I = img_ptrs(ws, L, b);
-    const int t = threadIdx.x;
-    const float* s = scores + (size_t)b * N;
-    const float4* bx = boxes ? reinterpret_cast<const float4*>(boxes) + (size_t)b * N : nullptr;
-    float zlo = 0.0f, zscale = 0.0f;
-    if (role == 1 && mode3d > 1) block_z_bands(bx, n, mode3d, &zlo, &zscale);
-    u64 k[4];
-    int flag = 1;                                                      // workgroup 0: role 0 "the scores came in sorted", role 1 "every box is plain"
-    if (role == 0) {
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (4 * t + 3 < N && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
-            const float4 q = reinterpret_cast<const float4*>(s)[t];
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) if (4 * t + e < n) v[e] = s[4 * t + e];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) k[e] = (4 * t + e < n) ? (((u64)gnms_desc_key(v[e]) << 32) | (unsigned)(4 * t + e)) : ~0ull;   // (sort_key_of)
-        if (r == 0) {                                                  // ascending keys in index order = the scores came in sorted
-            const u64 next = (4 * t + 4 < n) ? sort_key_of(0, s, nullptr, 4 * t + 4, 0, 0.0f, 0.0f) : ~0ull;
-            flag = (4 * t + 1 >= n || k[0] < k[1]) && (4 * t + 2 >= n || k[1] < k[2]) && (4 * t + 3 >= n || k[2] < k[3]) && (4 * t + 4 >= n || k[3] < next);
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int i = 4 * t + e;
-            k[e] = ~0ull;
-            if (i < n) {
-                const float4 v = bx[i];
-                k[e] = column_key(v, i, mode3d, zlo, zscale);
-                flag &= box_orders_plainly(v) ? 1 : 0;                 // (tested on the box the key is made of, as sort_count_body does)
-            }
-        }
-    }
-    wave_sort_256(k);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) keys[4 * t + e] = k[e];
-    // what only one workgroup per image and role does: the flags (it holds every key, so it decides alone), the counters, the call counter,
-    // the hand-off granules
-    if (r == 0) {
-        const int all = __syncthreads_and(flag);                       // (also: the runs are in LDS)
-        if (role == 0) {
-            if (t < 8 && !(boxes && t == 6)) I.misc[t] = (t == 2) ? all : 0;               // ([6]: the x sort's)
-            if (t == 8) I.misc[8] = gnms_next_epoch(I.misc[8]);
-            for (int i = t; i < 17 * 32; i += 1024) I.gran[i] = 0ull;
-        } else if (t == 0) {
-            I.misc[6] = all ? 0 : 1;
-        }
-    } else {
-        __syncthreads();
-    }
-    const int key = t & (kRankRunKeys - 1), quarter = t >> 8;
-    const u64 mine = keys[r * kRankRunKeys + key];
-    const bool live = mine != ~0ull;
-    const int idx = (int)((unsigned)mine & (role == 0 ? 0xffffffffu : kColIdxMask));
-    // what leaves with the key -- its score, its box -- is fetched by INPUT index, known before the searches: requested here (sort_merge_body)
-    float sv = 0.0f;
-    float4 bv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (quarter == 0 && live) {
-        if (role == 0) sv = s[idx];
-        if (bx) bv = bx[idx];
-    }
-    int cnt = 0;
-    if (live) {
-        const u64* q4 = keys + quarter * 4 * kRankRunKeys;             // the four runs of this quarter
-        int pos[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int h = kRankRunKeys / 2; h >= 1; h >>= 1) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pos[j] += (q4[j * kRankRunKeys + pos[j] + h - 1] < mine) ? h : 0;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) cnt += (quarter * 4 + j == r) ? key : pos[j] + ((q4[j * kRankRunKeys + pos[j]] < mine) ? 1 : 0);
-        if (quarter) part[quarter - 1][key] = cnt;
-    }
-    __syncthreads();
-    if (quarter == 0 && live) {
-        const int rank = cnt + part[0][key] + part[1][key] + part[2][key];
-        if (role == 0) {
-            I.order[rank] = idx;
-            I.rankof[idx] = rank;
-            I.sscore[rank] = sv;
-            if (bx) I.rbox[rank] = bv;                                 // (the from-boxes layer: row boxes of the bit matrix)
-            if (order_out) order_out[(size_t)b * N + rank] = idx;
-        } else {
-            column_store(I, rank, idx, bv, mode3d);
-        }
-    }
-    if (role == 0) {
-        const int kp = n + r * 1024 + t;                               // padding ranks map to themselves (order is a permutation of [0, N))
-        if (kp < N) {
-            I.order[kp] = kp; I.rankof[kp] = kp; I.sscore[kp] = 0.0f;
-            if (order_out) order_out[(size_t)b * N + kp] = kp;
-        }
-    }
 }
 
 __global__ __launch_bounds__(1024) void sort_ranked_runs_kernel(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
                                                                 const int* __restrict__ counts, char* ws, gnms_ws_layout L,
                                                                 long long* __restrict__ order_out, int mode3d) {
     sort_ranked_runs_body(scores, boxes, N, counts, ws, L, order_out, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, mode3d);
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// K1 for N <= 2048 (round 5): the same two sorts by COUNTING, spread over the machine.  Up to 1024 keys one workgroup per (image, role)
-// sorted them in LDS: 4-5 us of merge passes on one CU inside a 9-12-us launch that left 240 CUs idle -- the longest launch in front of the
-// chain at the reference's own sizes.  A key's position in the sorted order is the number of keys below it (keys are distinct: the index is
-// in the low bits), and that needs no sort at all: workgroup (block, image, role) takes 64 keys, every workgroup holds ALL keys of its
-// image in LDS, thread (key, segment) counts the keys of one sixteenth of the image below its own, an LDS atomic adds the sixteen counts,
-// and the 64 results leave exactly as the merge kernel's do.  N / 64 workgroups per image and role: 256 at B = 8, N = 1024.
-// ------------------------------------------------------------------------------------------------
-// FUSED (round 6, one_launch_kernel): the same workgroup as a ROLE of the one launch of a small image.  Nothing of the workspace is
-// zeroed or counted here (the launch's tag comes from its caller and the flags are strong granules, see there); everything another
-// workgroup of the launch reads leaves through agent-scope stores, and the workgroup's last act is its "sorted" flag.
-__device__ __forceinline__ u64 strong_gran(unsigned tag, unsigned slot) { return ((u64)tag << 32) | (u64)(unsigned)(~tag ^ (0x9E3779B9u * (slot + 1u))); }
-constexpr unsigned kSlotSort = 0u;       // + 32 * role + workgroup of the sort          -> gran[1 + role][workgroup]
-constexpr unsigned kSlotBits = 64u;      // + workgroup of the bit table (<= 416)        -> gran[3 .. 15][workgroup]
-constexpr unsigned kSlotVerdict = 512u;  // + the verdict (1 fast tail, 2 K5 proper ran) -> gran[16][kGranVerdict]
-
-template <int KPW, bool FUSED = false>   // keys per workgroup: 64, or 32 where that still is one round of the machine (B = 1, N = 4096: 10.5 -> ? us)
-__device__ __forceinline__ void sort_count_body(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
-                                                const int* __restrict__ counts, char* ws, gnms_ws_layout L,
-                                                long long* __restrict__ order_out, int mode3d, const int blk, const int b, const int role,
-                                                const unsigned tag = 0u) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* keys = reinterpret_cast<u64*>(smem);                          // [NP] all keys of the image (padding ~0: behind everything)
-    __shared__ int rk[64];
-    const int n = gnms_count(counts, b, N);
-    ImgPtrs I = img_ptrs(ws, L, b);
-    const int t = threadIdx.x, lane = t & (KPW - 1), seg = t / KPW;
-    const int NP = (N + 63) & ~63;
-    const float* s = scores + (size_t)b * N;
-    const float* bx = boxes ? boxes + (size_t)b * N * 4 : nullptr;
-    float zlo = 0.0f, zscale = 0.0f;
-    if (role == 1 && mode3d > 1) block_z_bands(reinterpret_cast<const float4*>(bx), n, mode3d, &zlo, &zscale);
-    const int k = blk * KPW + lane;                                    // (k < NP)
-    // key k is input index k: what leaves with it -- its score, its box -- needs no index from the sorted keys and is requested here, in front
-    // of everything (round 6: fetched by `idx` behind the count it was one more exposed memory round trip at the end of every workgroup)
-    float pre_s = 0.0f;
-    float4 pre_b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (seg == 0 && k < n) {
-        if (role == 0) pre_s = s[k];
-        if (bx) pre_b = reinterpret_cast<const float4*>(bx)[k];
-    }
-    int flag = 1;                                                      // role 1: "every box is plain" (workgroup 0 decides, below)
-    if (role == 0) {
-        for (int i = t; i < NP; i += 1024) keys[i] = (i < n) ? sort_key_of(0, s, bx, i, mode3d, zlo, zscale) : ~0ull;
-    } else {
-        // (the plain test on the box the key is made of: as a pass of its own over the boxes it was a second memory round trip of workgroup 0,
-        // the one every launch of this kernel ends with)
-        for (int i = t; i < NP; i += 1024) {
-            u64 key = ~0ull;
-            if (i < n) {
-                const float4 v = reinterpret_cast<const float4*>(bx)[i];
-                key = column_key(v, i, mode3d, zlo, zscale);
-                flag &= box_orders_plainly(v) ? 1 : 0;
-            }
-            keys[i] = key;
-        }
-    }
-    if (t < 64) rk[t] = 0;
-    __syncthreads();
-    const u64 mine = keys[k];
-    {
-        const int per = NP / (1024 / KPW);                             // a multiple of 4 (KPW = 32: the launcher asks for NP % 128 == 0)
-        const u64* p = keys + seg * per;
-        int c = 0;
-        for (int j = 0; j < per; j += 4) c += (p[j] < mine ? 1 : 0) + (p[j + 1] < mine ? 1 : 0) + (p[j + 2] < mine ? 1 : 0) + (p[j + 3] < mine ? 1 : 0);
-        if (c) atomicAdd(&rk[lane], c);
-    }
-    // what only one workgroup per image and role does: the "already sorted" / "every box is plain" flags (every workgroup holds every key,
-    // so the first one decides alone), the counters, the call counter, the hand-off granules
-    if (blk == 0 && role == 0) {
-        for (int i = t; i + 1 < n; i += 1024) flag &= keys[i] < keys[i + 1];          // ascending keys in index order = the scores came in sorted
-    }
-    const int all = __syncthreads_and(flag);                           // (also: every count has landed in rk)
-    if (blk == 0) {
-        if (role == 0) {
-            if constexpr (FUSED) {
-                if (t < 8 && !(boxes && t == 6)) coh_store(I.misc + t, (t == 2) ? all : 0);
-            } else {
-                if (t < 8 && !(boxes && t == 6)) I.misc[t] = (t == 2) ? all : 0;           // ([6]: the x sort's)
-                if (t == 8) I.misc[8] = gnms_next_epoch(I.misc[8]);
-                for (int i = t; i < 17 * 32; i += 1024) I.gran[i] = 0ull;
-            }
-        } else if (t == 0) {
-            if constexpr (FUSED) coh_store(I.misc + 6, all ? 0 : 1); else I.misc[6] = all ? 0 : 1;
-        }
-    }
-    if (seg == 0) {
-        if (k < n) {
-            const int rank = rk[lane];
-            const int idx = (int)((unsigned)mine & (role == 0 ? 0xffffffffu : kColIdxMask));
-            if (role == 0) {
-                if constexpr (FUSED) {
-                    coh_store(I.order + rank, idx);
-                    coh_store(I.rankof + idx, rank);
-                    coh_store(I.sscore + rank, pre_s);
-                    if (boxes) coh_store_f4(I.rbox + rank, pre_b);
-                } else {
-                    I.order[rank] = idx;
-                    I.rankof[idx] = rank;
-                    I.sscore[rank] = pre_s;
-                    if (boxes) I.rbox[rank] = pre_b;
-                }
-                if (order_out) order_out[(size_t)b * N + rank] = idx;
-            } else {
-                if constexpr (FUSED) {
-                    coh_store(I.xidx + rank, idx);
-                    coh_store_f4(I.xbox + rank, pre_b);
-                } else {
-                    column_store(I, rank, idx, pre_b, mode3d);
-                }
-            }
-        } else if (k < N && role == 0) {                               // padding ranks map to themselves (order is a permutation of [0, N))
-            if constexpr (FUSED) { coh_store(I.order + k, k); coh_store(I.rankof + k, k); coh_store(I.sscore + k, 0.0f); }
-            else { I.order[k] = k; I.rankof[k] = k; I.sscore[k] = 0.0f; }
-            if (order_out) order_out[(size_t)b * N + k] = k;
-        }
-    }
-    if constexpr (FUSED) {
-        __builtin_amdgcn_s_waitcnt(0x0f70);                            // vmcnt(0): this wave's stores are acknowledged ...
-        __syncthreads();                                               // ... every wave's are
-        if (t == 0) coh_store(I.gran + (size_t)(1 + role) * 32 + blk, strong_gran(tag, kSlotSort + 32u * (unsigned)role + (unsigned)blk));
-    }
-}
-
-template <int KPW>
-__global__ __launch_bounds__(1024) void sort_count_kernel(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
-                                                          const int* __restrict__ counts, char* ws, gnms_ws_layout L,
-                                                          long long* __restrict__ order_out, int mode3d) {
-    sort_count_body<KPW>(scores, boxes, N, counts, ws, L, order_out, mode3d, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -870,15 +56,6 @@ __global__ __launch_bounds__(1024) void sort_count_kernel(const float* __restric
 // ------------------------------------------------------------------------------------------------
 constexpr int kMaskWaves = 8;       // waves per workgroup: 8 x 256 = 2048 columns
 constexpr int kMaskRB = 8;          // rows (1-KiB loads) in flight per wave
-
-__device__ __forceinline__ float4 load_nt_f4(const float* p) {
-    float4 v;
-    v.x = __builtin_nontemporal_load(p);
-    v.y = __builtin_nontemporal_load(p + 1);
-    v.z = __builtin_nontemporal_load(p + 2);
-    v.w = __builtin_nontemporal_load(p + 3);
-    return v;
-}
 
 // Rows of W out of an LDS row buffer, WRITE-THROUGH (round 9): `words` words (a row of NC, or KBW adjacent rows: they are adjacent in W as
 // in LDS) from `src` to `dst`, every lane 16 bytes per pass -- ds_read_b128, one 16-byte buffer store with sc1 (aux = 16).  A plain store
@@ -1137,8 +314,6 @@ __device__ __forceinline__ void wsym_check_in_launch(int N, const int* __restric
 // areas and thr >= 0, inter = +0 and uni > 0 give 0 <= thr).  On detector-like inputs (boxes ~100 px on a 1760 px wide
 // canvas) a tile keeps 15-20 % of its 64 rows.  The price: the rank triangle can no longer be skipped per tile (a tile
 // holds columns of every rank); words no leader scan reads (column rank >= 64 (kb+1)) are computed but not stored.
-__device__ __forceinline__ float wave_min_f(float v) { return gnms_wave_min_f(v); }   // DPP network: no ds_bpermute round trips
-__device__ __forceinline__ float wave_max_f(float v) { return gnms_wave_max_f(v); }
 
 // CPL = columns per lane: 4 (wave tile 64 x 256) when there are plenty of tiles, 1 (64 x 64) for small problems, where the 64-row
 // chain of a wave is the critical path and four times as many waves share it.
@@ -1237,12 +412,9 @@ __device__ __forceinline__ void bitmask_boxes_body(const float* __restrict__ box
         cok &= (carea[j] > 0.0f) && (carea[j] < INFINITY);
     }
     }
-    // Decision !(fl(inter/uni) <= thr) WITHOUT the division.  With d = fma(-thr, uni, inter) (one rounding, sign exact):
-    //   inter/uni - thr = d/uni,  so  |d| > guard*uni  puts the exact quotient more than `guard` (8 ulp of the threshold)
-    // away from thr, hence its fp32 rounding on the same side, and the pair is decided by the sign of d.  That needs
-    // uni > 0 and finite, which holds whenever both boxes have a positive finite area (inter <= min(area) in fp32 as in
-    // exact arithmetic because subtraction/multiplication round monotonically, so uni >= max(area) > 0): checked once per
-    // column box and per row.  Rows/columns that fail, and the pairs inside the guard band, take the exact IEEE division.
+    // Decision !(fl(inter/uni) <= thr) WITHOUT the division: the sign of d = fma(-thr, uni, inter) outside the guard band (iou_guard_band,
+    // gnms_device.h: why 8 ulp suffice).  Positive finite areas are checked once per column box and per row; rows/columns that fail, and
+    // the pairs inside the guard band, take the exact IEEE division.
     // (KBW = 1: two workgroups per CU leave 64 VGPRs: the columns' ranks, not needed before the words are parked, wait in LDS meanwhile.
     // KBW = 2 is one workgroup per CU with 128 VGPRs: the four ranks stay in registers, their gather in flight behind the first rows loop)
     constexpr bool STASH = ROWBUF && !CHUNKLOOP && CPL == 4 && KBW == 1;
@@ -1251,7 +423,7 @@ __device__ __forceinline__ void bitmask_boxes_body(const float* __restrict__ box
 #pragma unroll
         for (int j = 0; j < CPL; ++j) crank_lds[j * 1024] = crank[j];
     }
-    const float guard = fmaxf(fabsf(thr), 1.0f) * 9.6e-7f;            // 8 ulp at the threshold's magnitude (>= 1 for tiny thresholds)
+    const float guard = iou_guard_band(thr);
     const bool cols_ok = __all(cok);
     const bool plain_img = I.misc[6] == 0;                            // (sort_boxes_by_x / sort_merge_body: no box that is not plain)
     // hull of the tile's columns
@@ -1377,13 +549,7 @@ __device__ __forceinline__ void bitmask_boxes_body(const float* __restrict__ box
                 bool unsure = false;
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
-                    // (v_min / v_max issued directly, the row coordinate straight from its SGPR: fminf / fmaxf on loaded values cost a
-                    // canonicalising v_max x, x each -- 12 of the ~85 VALU instructions of a row; same values, iou3d_pair.h)
-                    const float w = fmaxf(gnms_iou3d::vmin_s(ax2, cb[j].z) - gnms_iou3d::vmax_s(ax1, cb[j].x), 0.0f);
-                    const float h = fmaxf(gnms_iou3d::vmin_s(ay2, cb[j].w) - gnms_iou3d::vmax_s(ay1, cb[j].y), 0.0f);
-                    inter4[j] = w * h;
-                    uni4[j] = (aa + carea[j]) - inter4[j];                // row box is `a`, column (leader) box is `b`
-                    d4[j] = __builtin_fmaf(-thr, uni4[j], inter4[j]);
+                    iou_row_terms(ax1, ay1, ax2, ay2, aa, cb[j], carea[j], thr, inter4[j], uni4[j], d4[j]);
                     unsure |= !(fabsf(d4[j]) > guard * uni4[j]);          // also true for NaN
                 }
                 if (!(cols_ok && ((rows_ok >> r) & 1ull)) || __any(unsure)) {
@@ -1649,735 +815,10 @@ __global__ __launch_bounds__(256) void bitmask_rec3d_culled_kernel(int N, const 
 // B = 8, N = 16384 step 2.20 -> 2.33 ms, N = 8192 0.593 -> 0.616.  The scatter kernel stays.)
 
 // ------------------------------------------------------------------------------------------------
-// K3: leaders (= the boxes classical greedy NMS keeps).  The scan is inherently sequential over rank
-// blocks; what must NOT be on that sequential path is global-memory latency.  Ranks are processed in
-// super-blocks of kSB = 16 blocks (1024 ranks), software-pipelined inside ONE workgroup of 16 waves:
-//   * removed-words of ALL blocks live in LDS (accAll[NB]);
-//   * while wave 0 resolves super-block sb (registers + LDS only), waves 1..15 prefetch, for super-block
-//     sb+1, the speculative triangular table  Xs[(b,b')][lane] = W[b'][rank(b,lane)]  (what each candidate
-//     of block b would remove in blocks b' >= b of its own super-block): contiguous 512-B rows of W;
-//   * the new leaders' words are PUSHED into the removed-words of all later blocks by gathering, per target block, exactly the
-//     leaders' words (lane j = j-th leader of the super-block, from a list the resolve appends to): the 16 blocks of
-//     super-block sb+1 by all waves right after the resolve ("near", one block per wave, the only part the next resolve
-//     waits for), the blocks beyond by waves 1..15 WHILE wave 0 resolves sb+1 ("far").  B=8, N=4096: 28.6 -> 24.5 us.
-// Resolve of one block: lane b' carries the removed-word of block b'; the 64 ranks are resolved on the
-// scalar unit visiting only the leaders (s_ff1 on ~removed); each new leader ORs its table row into the
-// lanes of the later blocks of the super-block.
-// ------------------------------------------------------------------------------------------------
-constexpr int kSB = 16;
-constexpr int kSBPairs = kSB * (kSB + 1) / 2;
-constexpr int kTabPer = (kSBPairs * 64 + 959) / 960;            // table entries per prefetching thread (waves 1..15)
-
-#ifdef GNMS_TIMING   // developer instrumentation (tools/phase_ticks.py): s_memtime deltas of thread 0 (GNMS_RACC: thread 960) of image 0's workgroups
-// accumulate in LDS -- round 5: a global read-modify-write per marker stalled wave 0 for a memory round trip, which the next barrier then
-// waited for (every slot read ~1 us too long) -- and go to ws gx[] of image 0 once, at the end of the kernel (GNMS_TFLUSH)
-__device__ __forceinline__ long long* gnms_tbuf() { __shared__ long long buf[32]; return buf; }
-#define GNMS_TINIT() do { if (threadIdx.x < 32) gnms::gnms_tbuf()[threadIdx.x] = 0; __syncthreads(); } while (0)
-#define GNMS_TFLUSH(ws_, L_, img_) do { __syncthreads(); if (threadIdx.x < 32 && (img_) == 0 && gnms::gnms_tbuf()[threadIdx.x]) \
-        atomicAdd(reinterpret_cast<unsigned long long*>(gnms::img_ptrs(ws_, L_, 0).gx) + threadIdx.x, (unsigned long long)gnms::gnms_tbuf()[threadIdx.x]); } while (0)
-#define GNMS_T0() long long t__ = (long long)__builtin_amdgcn_s_memtime()
-#define GNMS_TACC(slot) do { long long n__ = (long long)__builtin_amdgcn_s_memtime(); if (threadIdx.x == 0 && b == 0) gnms::gnms_tbuf()[slot] += n__ - t__; t__ = n__; } while (0)   /* image 0's workgroup */
-#define GNMS_TACC_IF(cond, slot) do { long long n__ = (long long)__builtin_amdgcn_s_memtime(); if (threadIdx.x == 0 && (cond)) gnms::gnms_tbuf()[slot] += n__ - t__; t__ = n__; } while (0)
-#else
-#define GNMS_TINIT() do {} while (0)
-#define GNMS_TFLUSH(ws_, L_, img_) do {} while (0)
-#define GNMS_TACC_IF(cond, slot) do {} while (0)
-#define GNMS_T0() do {} while (0)
-#define GNMS_TACC(slot) do {} while (0)
-#endif
-
-// workgroup barrier that waits for this wave's LDS operations only (not for its global loads / stores, as __syncthreads does): for
-// hand-offs that live in LDS.  Beside the matrix writers the drain of a wave's stores takes microseconds.
-// (LDS-only fences around the barrier builtin, not inline asm with a "memory" clobber: behind the clobber the compiler re-derived
-// everything it had loaded from memory -- kernel arguments, counts[b] -- after EVERY barrier, ~1000 cycles per step of a loop of them)
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-__device__ __forceinline__ u64 uniform64(u64 v) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(v & 0xffffffffu));
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 readlane64(u64 v, int lane) {
-    const unsigned lo = __builtin_amdgcn_readlane((unsigned)(v & 0xffffffffu), lane);
-    const unsigned hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), lane);
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ int tri_index(int b, int bp) { return b * kSB - (b * (b - 1)) / 2 + (bp - b); }   // b <= bp < kSB
-
-// exclusive OR-scan across the lanes of a wave
-__device__ __forceinline__ u64 wave_or_exclusive_scan(u64 v, int lane) {
-    u64 up = shfl_up_u64(v, 1);                                     // lane i <- lane i-1
-    if (lane == 0) up = 0ull;
-    return gnms_or_scan64(up);                                      // DPP inclusive OR-scan (gnms_common.h)
-}
-
-__host__ __device__ __forceinline__ size_t leaders_lds_layout(int NB, size_t* off_acc, size_t* off_lm, size_t* off_cand, size_t* off_pair) {
-    size_t o = (size_t)kSBPairs * 64 * 8;                       // Xs
-    *off_acc = o; o += (size_t)((NB + 1) & ~1) * 8;             // accAll[NB]
-    *off_lm = o; o += (size_t)((NB + 1 + kSB) & ~1) * 8;        // leader masks of all blocks (+ kSB of padding the sym scan may read)
-    *off_cand = o; o += 2 * (size_t)kSB * 64 * 4 + 128;        // leader ranks of the last two super-blocks + their counts (sym scan: list, claims, stamps)
-    *off_pair = o; o += 2 * kSBPairs * 4;                       // pair -> (b, b')
-    return o;
-}
-
-// dynamic LDS of leaders_kernel / leaders_body for an image of NB rank blocks (the one definition every launch site uses)
-__host__ __device__ __forceinline__ size_t leaders_lds_size(int NB) {
-    size_t a, l, c, p;
-    return leaders_lds_layout(NB, &a, &l, &c, &p);
-}
-
-// epilogue of the leader scan, off the sequential path: leader lists, per-block words, running counts (lmask[nb] in LDS is final;
-// `scratch` = >= (8 + nb) ints of LDS nobody else uses any more)
-__device__ __forceinline__ void leaders_epilogue(const ImgPtrs& I, const u64* lmask, int nb, int* scratch) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // exclusive prefix of popcounts over blocks: thread i < nb owns block i (nb <= 256)
-    int cnt = (tid < nb) ? __builtin_popcountll(lmask[tid]) : 0;
-    const int inc = (int)gnms_add_scan32((unsigned)cnt);          // DPP prefix sum
-    int* wsum = scratch;
-    if (lane == 63 && wave < 4) wsum[wave] = inc;
-    __syncthreads();
-    int basew = 0;
-    for (int w = 0; w < 4; ++w) if (w < wave) basew += wsum[w];
-    const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    int* pfx = wsum + 8;                                          // [nb] exclusive prefix
-    if (tid < nb) {
-        pfx[tid] = basew + inc - cnt;
-        I.leadw[tid] = lmask[tid];
-        I.leadpfx[tid + 1] = basew + inc;
-    }
-    __syncthreads();
-    for (int kb = wave; kb < nb; kb += 16) {
-        const u64 mine = lmask[kb];
-        if ((mine >> lane) & 1ull) {
-            const int slot = pfx[kb] + __builtin_popcountll(mine & ((1ull << lane) - 1ull));
-            const int k = (kb << 6) + lane;
-            I.leadc[slot] = I.order[k];
-            I.leadr[slot] = k;
-        }
-    }
-    if (tid == 0) { I.misc[0] = total; I.leadpfx[0] = 0; }
-}
-
-// ------------------------------------------------------------------------------------------------
-// K3 for a SYMMETRIC thresholded matrix whose rows W holds in full (from-boxes / from-records bit matrices; a matrix
-// wsym_check_kernel passed) -- round 4: ONE WORKGROUP PER SUPER-BLOCK (16 blocks = 1024 ranks), the workgroups of an image on
-// different CUs, handing the leader masks down the chain.
-//
-// What a super-block's leaders depend on is small -- the leader masks of the super-blocks before it, 128 bytes each -- and what
-// turns those masks into "removed by an earlier leader" is large but has nothing sequential in it: rank (T, lane) overlaps a
-// leader of source block bb iff  W[bb][rank] & mask[bb] != 0  (the matrix is symmetric), one coalesced 512-byte row segment per
-// (source block, target block), 1 MiB per image at N = 4096, 16 MiB at 16384.  One workgroup per image pulled all of that through
-// one CU's memory pipeline (~24 bytes per clock measured: 60k of the scan's 120k ticks on uniform boxes) between resolves that 15 of
-// its 16 waves sat out.  Here workgroup j owns super-block j: it requests the row segments of source super-block s for its own 16
-// blocks BEFORE the masks of s exist (the addresses do not depend on them), takes the masks when the workgroup of s publishes them,
-// ANDs -- sources in ascending order, so the first hit of a rank is its claimer (rem[], what K4 used to compute) -- then resolves its
-// own super-block, publishes, and stores rem[] for its ranks.  The chain is nsb hand-offs long; everything heavy runs beside it.
-//
-// HAND-OFF.  A mask travels as two 8-byte granules {epoch, 32 mask bits} written by single write-through stores and polled with
-// agent-scope loads: a granule is valid iff its tag is the workspace's call counter (misc[8], advanced by the sort kernels of every
-// call -- so stale granules of earlier calls, or of earlier replays of a captured graph, never match; the same kernels also zero the
-// image's granules, so that whatever a recycled allocation held where they now lie cannot carry the tag by accident).
-// No fence anywhere: beside the matrix writers one agent-scope release costs more than the whole scan (nms_layer.hip).  rem[] goes
-// out through write-through stores as well and is read back (groups_body / attribute_*) with agent-scope loads; the workgroup of the
-// LAST super-block waits for the other workgroups' "rem stored" granules and carries on with K4..K6 of the image.
-// A workgroup only ever waits for workgroups with a LOWER block index (dispatched before it).
-//
-// RESOLVE (inside a super-block).  The leaders are the unique solution of
-//     L[r] = !ext[r]  &&  no q < r (same super-block) with L[q] and overlap(q, r).
-// Wave tb owns block tb and iterates: from the current masks of the blocks before it (LDS, read at immediate offsets) and its table
-// words t[bb] = W[kb0 + bb][rank (tb, lane)] (registers) it recomputes its own mask (the in-block fixed point of round 2), all 16
-// waves at once, one LDS barrier per step, until a step changes no mask; a wave whose earlier blocks did not change since it last
-// looked skips the step.  Block tb is exact after step tb + 1 at the latest, NMS inputs settle in 3-5 steps.  (What a step costs is
-// LDS and VALU issue, 16 waves on 4 SIMDs: ~250 cycles for the barrier, ~500 for the 16 x 15 mask reads, ~1000 for the AND/ORs --
-// tools/../build/mb/bar.hip -- so the parallel resolve is no faster than the scalar-unit resolve of round 2 per super-block; what it
-// buys is that no wave idles and nothing else has to be overlapped with it.)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 gran_load(const u64* p) {
-    return (u64)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void gran_store(u64* p, u64 v) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// rem[] as the leader scan leaves it: agent-scope accesses (see above; plain ones would do between kernels, these do everywhere)
-__device__ __forceinline__ int rem_load(const int* rem, int k) { return __hip_atomic_load(rem + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void rem_store(int* rem, int k, int v) { __hip_atomic_store(rem + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// The super-blocks [j0, j1) of image `b`, one after the other (j1 <= nsb of the image; workgroup `me` of the image's `nwg` chain
-// workgroups, which own contiguous ascending ranges -- so a workgroup only ever waits for workgroups with a lower index).  Returns true
-// in the workgroup that may go on with K4..K6 of the image: the one whose range ends with the image's last super-block, after every
-// rem[] entry of the image is visible to it.
-//
-// STAGE (round 5, the fast tail; STAGE = the overlap source, kFromMatrix / kFromBoxes / kFromRecords, or kNoStage): masked groups, hard sort.
-// The workgroup that resolved a super-block knows, per rank k, the leader lr = rem[k] that took it -- and with it everything K5 computes for
-// k as long as two things hold for the IMAGE: every leader is a member of its own group (overlap(L, L) > thr: any box of positive finite
-// area), so head == leader, and no group is longer than the cap, so every member is kept.  It therefore evaluates
-//     member = overlap(k, lr) > thr;  plead = prune(overlap);  pre = s_k - plead * s_lr  (s_k for a leader);  r2 = clamp(pre)
-// right behind its resolve, for its own 1024 ranks, beside the chain (the masks are out by then), and stores head / plead / pre / r2
-// write-through in front of its "rem stored" granule; a leader outside its own group raises the granule's `complex` bit.  The image's last
-// workgroup then only has to check the two conditions (fast_final_body) before K6 -- no sort of the groups on the path to the
-// probabilities -- and the groups' CSR the backward reads is built beside K6 by one more workgroup (csr_build_body).
-// Returns 0 in the workgroups that are done, 1 in the image's last one (2: STAGE and some leader is outside its own group).
-constexpr int kNoStage = -1;
-constexpr int kFastGroupMax = 256;   // longest group the fast tail handles (default cap: 101)
-constexpr int kGranVerdict = 30;     // gran[16][30]: the last workgroup's verdict for csr_build_body (payload 1 = fast tail, 2 = K5 ran, nothing to do)
-
-// FUSED (round 6, one_launch_kernel; a single super-block: j0 = 0, j1 = 1): sort, bit table and this chain are workgroups of ONE launch.
-// The sort's outputs are read with agent-scope loads (the caller has waited for the sort's flags); the super-block's table is not
-// gathered from W but copied from the image the table workgroups leave where W lies (one_launch_bits_*: already in this layout, word
-// (source block bb <= target block tb, target lane) = the bits M[target][source] -- the reference's own orientation, :250, so no
-// symmetry is assumed and none is checked), behind a wait for their `nflags` flags; `tag` = the launch's call counter value.
-template <int STAGE = kNoStage, bool FUSED = false>
-__device__ __forceinline__ int leaders_sb_body(int N, const int* __restrict__ counts, char* ws, gnms_ws_layout L, const int b, const int j0,
-                                               const int j1, const int me, const float* __restrict__ stage_src = nullptr, long stage_ld = 0,
-                                               const float stage_thr = 0.0f, const float stage_temp = 0.0f, const int stage_prune = 0,
-                                               const int Ppow2 = 0, const unsigned tag = 0u, const int nflags = 0, const size_t lds_side = 0,
-                                               const u64* __restrict__ ext0 = nullptr) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    size_t oa, ol, oc, op;
-    leaders_lds_layout(L.NB, &oa, &ol, &oc, &op);
-    u64* Xs = reinterpret_cast<u64*>(smem);                      // [kSBPairs][64] table of the own super-block
-    u64* lmask = reinterpret_cast<u64*>(smem + ol);              // [NB + kSB] leader masks: the earlier super-blocks' as they arrive, then the own
-    int* pair_b = reinterpret_cast<int*>(smem + op);             // [kSBPairs]
-    int* pair_bp = pair_b + kSBPairs;
-    int* stamp = reinterpret_cast<int*>(smem + oc);              // [1] the last resolve step that changed a mask
-    int* bstamp = stamp + 4;                                     // [kSB] per block of the super-block: the last step that changed its mask
-    const int n = gnms_count(counts, b, N);
-    ImgPtrs I = img_ptrs(ws, L, b);
-    // (the wave index through readfirstlane: as tid >> 6 it is a VECTOR value to the compiler, and every `bb < tb` below became a 64-bit
-    // lane mask in an SGPR pair -- 186 spilled SGPRs and a v_readlane / s_nop pair around every use)
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nb = (n + 63) >> 6;
-    const int nsb = max(1, (nb + kSB - 1) / kSB);                  // (an EMPTY image still has one -- empty -- super-block: leaders_chain's count; its
-                                                                   // workgroup must reach K4..K6, the only writers of the image's outputs)
-    const u64 below = (1ull << lane) - 1ull;
-    const bool last_wg = j1 == nsb;                                // this workgroup ends with the image's last super-block
-    int have = 0;                                                  // super-blocks [0, have) have their masks in lmask (workgroup-uniform)
-    int complex_img = 0;                                           // STAGE: a leader of this workgroup's ranks is outside its own group
-    const u64 epoch = FUSED ? ((u64)tag << 32) : ((u64)(unsigned)I.misc[8] << 32);
-    GNMS_T0();
-    // table layout: pair (source block bb <= target block tb) at tb (tb + 1) / 2 + bb -- a target's words are consecutive, so the wave
-    // that owns it reads them at immediate offsets from one base (the general scan's layout needs the triangular index per word:
-    // ~12 scalar instructions each, and sixteen waves share the CU's one scalar unit)
-    if (tid < kSB) for (int bb = 0; bb <= tid; ++bb) { pair_b[tid * (tid + 1) / 2 + bb] = bb; pair_bp[tid * (tid + 1) / 2 + bb] = tid; }
-    for (int i = tid; i < nb + kSB; i += 1024) lmask[i] = 0ull;
-    __syncthreads();
-    for (int j = j0; j < j1; ++j) {
-    const int kb0 = j * kSB;
-    const int nblk = min(kSB, nb - kb0);
-    const bool last_sb = j == nsb - 1;
-    // STAGE: what the rank needs of itself (score, input index, box) is requested before anything is waited for
-    float st_sk = 0.0f;
-    int st_ck = 0;
-    float4 st_bk = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (STAGE != kNoStage) {
-        const int kk = ((kb0 + (wave < nblk ? wave : 0)) << 6) + lane;
-        if constexpr (FUSED) {
-            // the whole image's order / scores (/ boxes) by rank into LDS, beside everything else (smem + lds_side): the rank's own values and,
-            // behind the resolve, its leader's come from there -- one gather level (the overlap entry) instead of two
-            int* ordA = reinterpret_cast<int*>(smem + lds_side);
-            float* sscA = reinterpret_cast<float*>(ordA + 1024);
-            float4* rbxA = reinterpret_cast<float4*>(smem + lds_side + 8192);
-            if (tid < n) {
-                ordA[tid] = coh_load(I.order + tid);
-                sscA[tid] = coh_load(I.sscore + tid);
-                if (STAGE == kFromBoxes) rbxA[tid] = coh_load_f4(I.rbox + tid);
-            }
-        } else if (wave < nblk && kk < n) {
-            st_sk = I.sscore[kk];
-            st_ck = I.order[kk];
-            if (STAGE == kFromBoxes) st_bk = I.rbox[kk];
-        }
-    }
-    if (tid == 0) *stamp = 0;
-    if (tid < kSB) bstamp[tid] = -1;
-    {   // the own super-block's table: no dependence on anybody (in flight while the first masks are waited for)
-        constexpr int kTabAll = (kSBPairs * 64 + 1023) / 1024;
-        u64 tw[kTabAll];
-        if constexpr (FUSED) {                                     // the table workgroups' flags, then their image of the table as it stands
-            if (wave == 0) {
-                for (int f0 = 0; f0 < nflags; f0 += 64) {         // (<= 13 x 32 flags: gran[3 .. 15])
-                    const int f = f0 + lane < nflags ? f0 + lane : f0;
-                    const u64 want = strong_gran(tag, kSlotBits + (unsigned)f);
-                    const u64* g = I.gran + (size_t)3 * 32 + f;
-                    while (__ballot(gran_load(g) != want) != 0ull) __builtin_amdgcn_s_sleep(1);
-                }
-            }
-            __syncthreads();
-            if constexpr (STAGE != kNoStage) {
-                const int kk = ((kb0 + (wave < nblk ? wave : 0)) << 6) + lane;
-                if (wave < nblk && kk < n) {
-                    st_sk = reinterpret_cast<const float*>(smem + lds_side + 4096)[kk];
-                    st_ck = reinterpret_cast<const int*>(smem + lds_side)[kk];
-                    if (STAGE == kFromBoxes) st_bk = reinterpret_cast<const float4*>(smem + lds_side + 8192)[kk];
-                }
-            }
-            const int npw = (nb * (nb + 1) / 2) * 64;              // the image's pairs (target block < nb): what the table workgroups wrote
-#pragma unroll
-            for (int u = 0; u < kTabAll; ++u) {
-                const int e = tid + u * 1024;
-                tw[u] = (e < npw) ? coh_load(I.W + e) : 0ull;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < kTabAll; ++u) {
-                const int e = tid + u * 1024;
-                tw[u] = 0ull;
-                if (e < kSBPairs * 64) {
-                    const int pr = e >> 6;
-                    const int bb = pair_b[pr], bp = pair_bp[pr];
-                    const int k = (kb0 + bp) * 64 + (e & 63);      // row block = the SOURCE block bb, column = target rank (bp, lane)
-                    if (bp < nblk && k < n) tw[u] = I.W[(size_t)(kb0 + bb) * L.NC + k];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kTabAll; ++u) {
-            const int e = tid + u * 1024;
-            if (e < kSBPairs * 64) Xs[e] = tw[u];
-        }
-    }
-    GNMS_TACC_IF(b == 0 && last_sb, 0);
-    const int tb = wave;                                           // this wave's block of the super-block
-    const bool live = tb < nblk;
-    const int kT = ((kb0 + (live ? tb : 0)) << 6) + lane;          // this lane's rank
-    lds_barrier();                                                 // the table is in LDS (and the previous super-block of this workgroup is done with it and the stamps)
-    // ---- resolve of the own super-block: every wave its block, steps until no mask changes ----
-#ifdef GNMS_TIMING
-    long long r__ = (long long)__builtin_amdgcn_s_memtime();
-#define GNMS_RACC(slot) do { long long n__ = (long long)__builtin_amdgcn_s_memtime(); if (threadIdx.x == 960 && b == 0 && last_sb) gnms_tbuf()[slot] += n__ - r__; r__ = n__; } while (0)
-#else
-#define GNMS_RACC(slot) do {} while (0)
-#endif
-    const int tbc = live ? tb : 0;
-    const int k0 = (kb0 + tbc) << 6;
-    u64 tailmask = 0ull;                                           // past the image's last rank: never leaders
-    if (live) { const int nrows = min(64, n - k0); if (nrows < 64) tailmask = ~((1ull << nrows) - 1ull); }
-    const u64* myX = Xs + (size_t)(tbc * (tbc + 1) / 2) * 64 + lane;   // this wave's table words: source block bb at myX[bb * 64]
-    const u64* myL = lmask + kb0;                                  // (lmask is padded by kSB entries: no clamp)
-    const u64 cs = live ? (myX[tbc * 64] & below) : 0ull;          // earlier ranks of the block that overlap rank k0 + lane
-    unsigned tlo[kSB - 1], thi[kSB - 1];
-#pragma unroll
-    for (int bb = 0; bb < kSB - 1; ++bb) {                          // (entries past tb belong to other targets: masked)
-        const u64 x = myX[bb * 64];
-        tlo[bb] = (bb < tb) ? (unsigned)(x & 0xffffffffu) : 0u;
-        thi[bb] = (bb < tb) ? (unsigned)(x >> 32) : 0u;
-    }
-    u64 mine = 0ull;                                               // this block's leader mask as last published (lmask[kb0 + tb])
-    GNMS_RACC(21);
-    // (Round 5 ran this fixed point SPECULATIVELY while the workgroup waits -- cold with no external removals, then warm after every source
-    // ANDed in -- so that only a confirming step or two would be left behind the last source's masks.  Measured: no gain; on NMS inputs every
-    // source removes ranks in all 16 blocks, the repair cascades through the blocks like a cold resolve (17 steps in all where there were 4,
-    // the final call as long as before, the chain 10 k ticks longer).  One call, behind the last source.)
-    u64 cur_prev = ~0ull;
-    bool first = true;
-    int looked = 0;                                                // the step of this wave's last look at the earlier masks
-    int step = 1;
-    auto resolve = [&](const u64 ext) {
-        const u64 fixed = ext | tailmask;                          // never leaders: taken by earlier super-blocks, or past the image's last rank
-        bool force = true;
-        for (;;) {
-            if (live) {                                            // (wave-uniform)
-                // did a block before mine change since I last looked?  (lane bb holds block bb's stamp)
-                const bool dirty = force || __ballot(lane < tb && bstamp[lane < kSB ? lane : 0] >= looked) != 0ull;
-                if (dirty) {
-                    looked = step;
-                    unsigned vlo = 0u, vhi = 0u;
-                    if (!first) {                                  // (the very first look finds every mask of the super-block still zero)
-#pragma unroll
-                        for (int bb = 0; bb < kSB - 1; ++bb) {      // (one batch of reads: behind a branch per group of blocks they serialise)
-                            const u64 l = myL[bb];
-                            vlo |= tlo[bb] & (unsigned)(l & 0xffffffffu);
-                            vhi |= thi[bb] & (unsigned)(l >> 32);
-                        }
-                    }
-                    const u64 cur = fixed | __ballot((vlo | vhi) != 0u);
-                    GNMS_RACC(22);
-                    if (first || cur != cur_prev) {                // (the same `cur` gives the same leaders)
-                        cur_prev = cur;
-                        u64 leaders = 0ull;
-                        if (~cur != 0ull) {
-                            const bool cand = ((cur >> lane) & 1ull) == 0ull;
-                            leaders = ~cur;
-                            for (;;) {                             // in-block fixed point: positions < t are final after t rounds
-                                const u64 nl = __ballot(cand && (cs & leaders) == 0ull);
-                                if (nl == leaders) break;
-                                leaders = nl;
-                            }
-                        }
-                        if (leaders != mine) {
-                            mine = leaders;
-                            if (lane == 0) { lmask[kb0 + tb] = leaders; bstamp[tb] = step; *stamp = step; }
-                        }
-                    }
-                    first = false;
-                    GNMS_RACC(23);
-                }
-            }
-            force = false;
-            lds_barrier();
-            GNMS_RACC(24);
-            const int last = *stamp;
-            ++step;
-            if (step - last > 1) break;                            // a whole step without a change (a faster wave may have stamped a later step: still <=)
-        }
-    };
-    // ---- the earlier super-blocks, in ascending order: row segments requested, masks awaited, ANDed ----
-    int cl = -1;                                                   // rank of the first leader (of an earlier super-block) that overlaps it
-    for (int s = 0; s < j; ++s) {
-        const int s0 = s * kSB;
-        u64 wv[kSB];
-#pragma unroll
-        for (int bb = 0; bb < kSB; ++bb) wv[bb] = (live && kT < n) ? I.W[(size_t)(s0 + bb) * L.NC + kT] : 0ull;
-        if (wave == 0 && s >= have) {                              // the masks of super-block s (another workgroup's, not seen yet): 32 granules, lane g polls granule g
-            const u64* g = I.gran + (size_t)s * 32 + (lane & 31);
-            u64 v = gran_load(g);
-            while (__ballot((v & 0xffffffff00000000ull) != epoch) != 0ull) { __builtin_amdgcn_s_sleep(2); v = gran_load(g); }
-            reinterpret_cast<unsigned*>(lmask + s0)[lane & 31] = (unsigned)(v & 0xffffffffu);   // (lanes 32..63 write the same words again)
-        }
-        lds_barrier();
-        int c = -1;
-#pragma unroll
-        for (int bb = 0; bb < kSB; ++bb) {
-            const u64 m = wv[bb] & lmask[s0 + bb];
-            if (c < 0 && m != 0ull) c = ((s0 + bb) << 6) + __builtin_ctzll(m);
-        }
-        if (cl < 0) cl = c;
-    }
-    if (j + 1 > have) have = j + 1;                                // (every super-block up to j is in lmask from here on: polled above, or this workgroup's own)
-    // (ext0, classical NMS in chunks -- classic_nms.hip: word kb of it = ranks of block kb that something OUTSIDE this scan has removed already)
-    const u64 ext = __ballot(cl >= 0) | ((ext0 != nullptr && live) ? ext0[kb0 + tbc] : 0ull);   // removed-word of the wave's block (earlier super-blocks' leaders)
-    GNMS_TACC_IF(b == 0 && last_sb, 1);
-    if constexpr (FUSED) {
-        // A single super-block with nobody to hand masks to: ONE wave walks the blocks in order -- lane = rank of the block, the table words of
-        // block t2 against the masks of the blocks before it (wave-uniform: scalar registers), then the in-block fixed point -- no barrier and no
-        // repeated steps: ~150-300 cycles per block where the sixteen-wave fixed point above takes 4-7 steps of ~1200 (N = 500: 4.3 -> ~1 us)
-        if (wave == 0) {
-            u64 m[kSB];
-#pragma unroll
-            for (int t2 = 0; t2 < kSB; ++t2) {
-                m[t2] = 0ull;
-                if (t2 < nblk) {                                   // (wave-uniform)
-                    const u64* X = Xs + (size_t)(t2 * (t2 + 1) / 2) * 64 + lane;
-                    u64 hit = 0ull;
-#pragma unroll
-                    for (int bb = 0; bb < t2; ++bb) hit |= X[bb * 64] & m[bb];
-                    const u64 csq = X[t2 * 64] & below;
-                    const int nr = min(64, n - ((kb0 + t2) << 6));
-                    const u64 cur = __ballot(hit != 0ull) | (nr < 64 ? ~((1ull << nr) - 1ull) : 0ull);
-                    u64 leaders = ~cur;
-                    if (leaders != 0ull) {
-                        const bool cand = ((cur >> lane) & 1ull) == 0ull;
-                        for (;;) {                                 // in-block fixed point: positions < t are final after t rounds
-                            const u64 nl = __ballot(cand && (csq & leaders) == 0ull);
-                            if (nl == leaders) break;
-                            leaders = nl;
-                        }
-                    }
-                    m[t2] = leaders;
-                    if (lane == 0) lmask[kb0 + t2] = leaders;
-                }
-            }
-        }
-        lds_barrier();
-        mine = live ? lmask[kb0 + tb] : 0ull;
-    } else {
-        resolve(ext);
-    }
-#ifdef GNMS_TIMING
-    if (threadIdx.x == 0 && b == 0 && last_sb) gnms_tbuf()[20] += step;
-#endif
-    // ---- publish the masks (the chain's critical path ends here), then rem[] ----
-    if (!last_sb && wave == 0 && lane < 32) {
-        const unsigned half = reinterpret_cast<const unsigned*>(lmask + kb0)[lane];
-        gran_store(I.gran + (size_t)j * 32 + lane, epoch | half);
-    }
-    GNMS_TACC_IF(b == 0 && last_sb, 2);
-    // rem[] of the wave's block: itself for a leader, else the first claimer -- an earlier super-block's (cl), else the first earlier
-    // block of this super-block with a leader in the table word, else the own block
-    {
-        const int k = k0 + lane;
-        int c = -1;
-#pragma unroll
-        for (int bb = 0; bb < kSB - 1; ++bb) {
-            const u64 l = myL[bb];
-            const unsigned mlo = tlo[bb] & (unsigned)(l & 0xffffffffu), mhi = thi[bb] & (unsigned)(l >> 32);
-            if (c < 0 && (mlo | mhi) != 0u) c = ((kb0 + bb) << 6) + (mlo ? __builtin_ctz(mlo) : 32 + __builtin_ctz(mhi));
-        }
-        if (c < 0) { const u64 m = cs & mine; c = (m != 0ull) ? k0 + __builtin_ctzll(m) : k; }
-        int r = k;
-        if (((mine >> lane) & 1ull) == 0ull) r = ((ext >> lane) & 1ull) ? cl : c;
-        if constexpr (STAGE != kNoStage) {
-            // the last workgroup's last super-block stays in LDS for fast_final_body (the table is dead: every wave has passed a barrier behind
-            // its last read of it): r2, head and input index by rank
-            const bool park = last_wg && j == j1 - 1;
-            float* r2L = reinterpret_cast<float*>(smem);                             // (finalize_fast_body's layout)
-            int* hdL = reinterpret_cast<int*>(smem + (size_t)Ppow2 * 4);
-            int* ordL = reinterpret_cast<int*>(smem + (size_t)Ppow2 * 8);
-            if (live && k < n) {
-                const int lr = r;
-                float sl = st_sk, ov;
-                if (STAGE == kFromBoxes) {
-                    float4 bl = st_bk;
-                    if (lr != k) {
-                        if constexpr (FUSED) { bl = reinterpret_cast<const float4*>(smem + lds_side + 8192)[lr]; sl = reinterpret_cast<const float*>(smem + lds_side + 4096)[lr]; }
-                        else { bl = I.rbox[lr]; sl = I.sscore[lr]; }
-                    }
-                    ov = pair_iou(st_bk, bl);
-                } else {
-                    int cb = st_ck;
-                    if (lr != k) {
-                        if constexpr (FUSED) { cb = reinterpret_cast<const int*>(smem + lds_side)[lr]; sl = reinterpret_cast<const float*>(smem + lds_side + 4096)[lr]; }
-                        else { cb = I.order[lr]; sl = I.sscore[lr]; }
-                    }
-                    ov = overlap_at<STAGE>(overlap_src<STAGE>(stage_src, I, b, N, stage_ld), stage_ld, st_ck, cb, stage_thr);
-                }
-                float pre = 0.0f, pl = 0.0f;
-                int hd = -1;
-                if (ov > stage_thr) {                              // strict > (:249)
-                    hd = lr;
-                    if (lr == k) pre = st_sk;
-                    else { pl = gnms_prune(ov, stage_thr, stage_temp, stage_prune); pre = st_sk - pl * sl; }
-                } else if (lr == k) complex_img = 1;               // a leader outside its own group (NaN / <= thr diagonal): K5 proper decides the heads
-                const float r2 = pre < 0.0f ? 0.0f : (pre > 1.0f ? 1.0f : pre);      // torch.clamp keeps NaN
-                if (park) { r2L[k] = r2; hdL[k] = hd; ordL[k] = st_ck; }
-                rem_store(I.rem, k, r);
-                rem_store(I.head, k, hd);
-                __hip_atomic_store(I.plead + k, pl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(I.pre + k, pre, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(I.r2 + k, r2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        } else {
-            if (live && k < n) rem_store(I.rem, k, r);
-        }
-    }
-    GNMS_TACC_IF(b == 0 && last_sb, 4);
-    }   // super-blocks of this workgroup
-    if (!last_wg) {
-        // every wave waits for the acknowledgement of its OWN write-through stores (s_waitcnt vmcnt(0): the barrier alone is an
-        // s_barrier, which orders nothing in memory -- ADVICE r4), then the barrier, then "rem stored" goes out
-        __builtin_amdgcn_s_waitcnt(0x0f70);                        // vmcnt(0) (gfx9 encoding: vmcnt = bits 3:0 + 15:14; expcnt / lgkmcnt left at their maxima)
-        const int cx = (STAGE != kNoStage) ? __syncthreads_or(complex_img) : (__syncthreads(), 0);
-        if (tid == 0) gran_store(I.gran + (size_t)16 * 32 + me, epoch | 1ull | (cx ? 2ull : 0ull));
-        return 0;
-    }
-    // ---- the image's last super-block: the other workgroups' rem[] must be there, then the per-image epilogue (all masks are in LDS) ----
-    if (wave == 0 && me > 0) {
-        const u64* g = I.gran + (size_t)16 * 32 + (lane < me ? lane : 0);
-        u64 v = gran_load(g);
-        while (__ballot((v & 0xffffffff00000000ull) != epoch) != 0ull) { __builtin_amdgcn_s_sleep(2); v = gran_load(g); }
-        if (STAGE != kNoStage && __ballot((v & 2ull) != 0ull) != 0ull) complex_img = 1;
-    }
-    GNMS_TACC_IF(b == 0 && last_wg, 3);
-    if constexpr (STAGE != kNoStage) {
-        return __syncthreads_or(complex_img) ? 2 : 1;              // (leaders_epilogue: only the slow path needs the lists -- fast_final_body)
-    } else {
-        __syncthreads();
-        leaders_epilogue(I, lmask, nb, reinterpret_cast<int*>(Xs));
-        GNMS_TACC_IF(b == 0 && last_wg, 4);
-        return 1;
-    }
-}
-
-// The four per-image stages K3..K6 are written as device functions (`*_body`, 1024 threads, image index `b`) so that they
-// run either as kernels of their own (thin wrappers below) or back to back inside ONE launch (tail_kernel).
-// leaders_body: the GENERAL scan (matrix in, possibly asymmetric; classical NMS), one workgroup per image.  Table entry
-// (b, b')[lane] = W[b'][rank(b, lane)], what candidate (b, lane) would remove in block b', pushed leader by leader; wave 0 resolves on
-// the scalar unit (~130 cycles per leader) while waves 1..15 prefetch and push.  Symmetric matrices take leaders_sb_body above.
-__device__ __forceinline__ void leaders_body(int N, const int* __restrict__ counts, char* ws, gnms_ws_layout L, const int b) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    size_t oa, ol, oc, op;
-    leaders_lds_layout(L.NB, &oa, &ol, &oc, &op);
-    u64* Xs = reinterpret_cast<u64*>(smem);                      // [kSBPairs][64]
-    u64* accAll = reinterpret_cast<u64*>(smem + oa);             // [NB]
-    u64* lmask = reinterpret_cast<u64*>(smem + ol);              // [NB]
-    int* pair_b = reinterpret_cast<int*>(smem + op);             // [kSBPairs]
-    int* pair_bp = pair_b + kSBPairs;
-    int* llist = reinterpret_cast<int*>(smem + oc);              // [2][kSB * 64] ranks of the leaders of super-block sb (buffer sb & 1)
-    int* lcount = llist + 2 * kSB * 64;                          // [2]
-    const int n = gnms_count(counts, b, N);
-    ImgPtrs I = img_ptrs(ws, L, b);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nb = (n + 63) >> 6;
-    const int nsb = (nb + kSB - 1) / kSB;
-    GNMS_T0();
-    if (tid < kSB) for (int bp = tid; bp < kSB; ++bp) { pair_b[tri_index(tid, bp)] = tid; pair_bp[tri_index(tid, bp)] = bp; }
-    for (int i = tid; i < nb; i += 1024) { accAll[i] = 0ull; lmask[i] = 0ull; }
-    __syncthreads();
-
-    // table prefetch of super-block `sb` into registers, by the threads [first, 1024)
-    u64 tw[kTabPer];
-    auto table_load = [&](int sb, int first, int nthr) {
-        const int kb0 = sb * kSB;
-        const int nblk = min(kSB, nb - kb0);
-#pragma unroll
-        for (int u = 0; u < kTabPer; ++u) {
-            const int e = (tid - first) + u * nthr;
-            tw[u] = 0ull;
-            if (tid >= first && e < kSBPairs * 64) {
-                const int pr = e >> 6;
-                const int bb = pair_b[pr], bp = pair_bp[pr];
-                if (bp < nblk) {
-                    // row block = the target block bp, column = candidate rank (bb, lane): contiguous 512 B per (b, b') row
-                    const int k = (kb0 + bb) * 64 + (e & 63);
-                    if (k < n) tw[u] = I.W[(size_t)(kb0 + bp) * L.NC + k];
-                }
-            }
-        }
-    };
-    auto table_store = [&](int first, int nthr) {
-#pragma unroll
-        for (int u = 0; u < kTabPer; ++u) {
-            const int e = (tid - first) + u * nthr;
-            if (tid >= first && e < kSBPairs * 64) Xs[e] = tw[u];
-        }
-    };
-    // prologue: table of super-block 0 (waves 1..15 so the register footprint is the same as in the loop)
-    table_load(0, 64, 960);
-    table_store(64, 960);
-    __syncthreads();
-    GNMS_TACC(0);
-
-    // push: OR the words of super-block `src`'s leaders into the removed-words of the blocks [first, last); the calling waves are
-    // numbered w of nw and take every nw-th block, four blocks at a time.  Lane j gathers the word of the j-th leader (the resolve
-    // appends every leader to a list as it finds it) -- exactly the words that matter, and all of a wave's blocks in ONE memory
-    // round trip.
-    auto push = [&](int src, int first, int last, int w, int nw) {
-        const int* list = llist + (src & 1) * (kSB * 64);
-        const int nl = lcount[src & 1];
-        for (int base = first + w; base < last; base += 4 * nw) {
-            u64 a[4] = {0ull, 0ull, 0ull, 0ull};
-            for (int j0 = 0; j0 < nl; j0 += 64) {
-                const int j = j0 + lane;
-                const int lr = (j < nl) ? list[j] : -1;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int kbp = base + u * nw;
-                    if (lr >= 0 && kbp < last) a[u] |= I.W[(size_t)kbp * L.NC + lr];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int kbp = base + u * nw;
-                if (kbp < last) {                                  // wave-uniform
-                    const u64 acc = gnms_wave_or(a[u]);
-                    if (lane == 0 && acc != 0ull) atomicOr(reinterpret_cast<unsigned long long*>(&accAll[kbp]), (unsigned long long)acc);
-                }
-            }
-        }
-    };
-
-    // Per super-block sb:  wave 0 resolves it (registers and LDS only) WHILE waves 1..15 prefetch the table of sb+1 and push the
-    // leaders of sb-1 into the blocks from super-block sb+1 on ("far" push: nothing the running resolve reads);  then all 16 waves
-    // push the new leaders of sb into the 16 blocks of super-block sb+1 ("near" push, one block per wave), the only part of the
-    // push the next resolve has to wait for.
-    for (int sb = 0; sb < nsb; ++sb) {
-        const int kb0 = sb * kSB;
-        const int nblk = min(kSB, nb - kb0);
-        if (wave != 0) {
-            if (sb + 1 < nsb) table_load(sb + 1, 64, 960);
-            if (sb >= 1) push(sb - 1, (sb + 1) * kSB, nb, wave - 1, 15);
-        } else {
-            // ---- sequential resolve of this super-block: registers and LDS only ----
-            u64 myacc = (lane < nblk) ? accAll[kb0 + lane] : 0ull;     // lane b' = removed-word of block kb0+b'
-            u64 mylead = 0;                                            // lane b' = leader mask of block kb0+b'
-            int* list = llist + (sb & 1) * (kSB * 64);
-            int filled = 0;                                            // leaders of this super-block so far (wave-uniform)
-            for (int bb = 0; bb < nblk; ++bb) {
-                const int k0 = (kb0 + bb) << 6;
-                const int nrows = min(64, n - k0);
-                u64 cur = readlane64(myacc, bb);
-                if (nrows < 64) cur |= ~((1ull << nrows) - 1ull);     // ranks >= n never lead
-                if (~cur == 0ull) continue;                            // everything in this block is already removed
-                const u64 d = Xs[tri_index(bb, bb) * 64 + lane];       // what rank k0+lane removes inside its own block
-                // lane b' (> bb) also ORs the table row of every new leader into its removed-word; the LDS read of
-                // leader i is consumed one trip later, so its latency hides behind the scalar chain of leader i+1
-                const bool tgt = lane > bb && lane < nblk;
-                const u64* row = Xs + (size_t)tri_index(bb, tgt ? lane : bb) * 64;
-                u64 leaders = 0, pend = 0;
-                do {                                                   // scalar loop: one trip per leader
-                    const int p = __builtin_ctzll(~cur);
-                    leaders |= 1ull << p;
-                    const u64 nxt = row[p];
-                    cur |= readlane64(d, p) | (1ull << p);             // a leader always leaves `remaining`
-                    myacc |= tgt ? pend : 0ull;
-                    pend = nxt;
-                } while (~cur != 0ull);
-                myacc |= tgt ? pend : 0ull;
-                if (lane == bb) mylead = leaders;
-                // the block's leaders join the list the pushes gather by (`leaders` is wave-uniform: one masked LDS store)
-                if ((leaders >> lane) & 1ull) list[filled + __builtin_popcountll(leaders & ((1ull << lane) - 1ull))] = k0 + lane;
-                filled += __builtin_popcountll(leaders);
-            }
-            if (lane < nblk) lmask[kb0 + lane] = mylead;
-            if (lane == 0) lcount[sb & 1] = filled;
-        }
-        GNMS_TACC(1);
-        __syncthreads();                                               // (A) wave 0 is done with Xs; the far pushes have landed
-        GNMS_TACC(2);
-        push(sb, kb0 + nblk, min(kb0 + nblk + kSB, nb), wave, 16);
-        if (sb + 1 < nsb) table_store(64, 960);                        // land the prefetched table for the next super-block
-        GNMS_TACC(3);
-        __syncthreads();                                               // (B)
-        GNMS_TACC(4);
-    }
-    leaders_epilogue(I, lmask, nb, reinterpret_cast<int*>(Xs));
-}
-
-// One CHAIN workgroup of a launch that runs the leader scan of B images with `spw` workgroups per image (spw = ceil(NB / 16) when the
-// launch may meet symmetric images -- leaders_chain_wgs --, else 1); chain index c = (workgroup of the image) * B + image, so that the
-// workgroups of the first super-blocks, which wait for nobody, are dispatched first.  sym_arg: 0 general, 1 symmetric (W holds full
-// rows), 2 as wsym_check_kernel found this image's matrix.  Returns true, with *image set, in the ONE workgroup per image that goes
-// on with K4..K6.
-// workgroups per image: one per super-block, at most `cap` (0: no cap).  The launches that run beside a matrix write of their own
-// (large images) cap it so that the chain leaves the writers their CUs.
-__host__ __device__ inline int leaders_chain_wgs(int N, int sym_arg, int cap = 0) {
-    const int nsb = max(1, ((N + 63) / 64 + kSB - 1) / kSB);
-    const int w = sym_arg ? nsb : 1;
-    return (cap > 0 && w > cap) ? cap : w;
-}
-
-// Returns 0 in the workgroups that are done; in the ONE workgroup per image that goes on with K4..K6: 1 (symmetric scan; with STAGE the
-// fast tail's values are stored, see leaders_sb_body), 2 (the same, but some leader is outside its own group), 3 (general scan).
-template <int STAGE = kNoStage>
-__device__ __forceinline__ int leaders_chain(int N, const int* __restrict__ counts, char* ws, gnms_ws_layout L, const int B, const int spw,
-                                             const int c, const int sym_arg, int* image, const float* __restrict__ stage_src = nullptr,
-                                             long stage_ld = 0, const float stage_thr = 0.0f, const float stage_temp = 0.0f,
-                                             const int stage_prune = 0, const int Ppow2 = 0, const u64* __restrict__ ext0 = nullptr) {
-    const int jw = c / B, b = c - jw * B;
-    *image = b;
-    // sym_arg: 0 general, 1 symmetric, 2 as wsym_check_kernel found, 3 symmetric on trust (the check runs in this launch: wsym_check_in_launch)
-    const int sym = sym_arg == 2 ? (img_ptrs(ws, L, b).misc[3] == 0 ? 1 : 0) : (sym_arg == 3 ? (img_ptrs(ws, L, b).misc[2] == 0 ? 1 : 0) : sym_arg);
-    if (!sym) {
-        if (jw != spw - 1) return 0;
-        leaders_body(N, counts, ws, L, b);
-        return 3;
-    }
-    // symmetric: the image's own super-blocks (ragged counts: fewer than the launch provides for) in contiguous ranges of q
-    const int n = gnms_count(counts, b, N);
-    const int nsb = max(1, (((n + 63) >> 6) + kSB - 1) / kSB);
-    const int q = (nsb + spw - 1) / spw;
-    const int j0 = jw * q, j1 = min(nsb, j0 + q);
-    if (j0 >= j1) return 0;                                        // (workgroup-uniform)
-    return leaders_sb_body<STAGE>(N, counts, ws, L, b, j0, j1, jw, stage_src, stage_ld, stage_thr, stage_temp, stage_prune, Ppow2, 0u, 0, 0, ext0);
-}
-
-__global__ __launch_bounds__(1024) void leaders_kernel(int N, const int* __restrict__ counts, char* ws, gnms_ws_layout L, int sym, int B, int spw,
-                                                       const u64* __restrict__ ext0 = nullptr) {
-    int b;
-    leaders_chain(N, counts, ws, L, B, spw, (int)blockIdx.x, sym, &b, nullptr, 0, 0.0f, 0.0f, 0, 0, ext0);
-}
-
-// ------------------------------------------------------------------------------------------------
 // K4: attribution.  One wave per rank block: walk the leaders with rank < 64(kb+1) in order, 64 per step;
 // an exclusive OR-scan across lanes tells each leader which bits it is the FIRST to claim.
 //   rem[k] = rank of the leader that removed rank k (k itself for a leader), gpos[k] = that leader's ordinal.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 slab_col(const ImgPtrs& I, const gnms_ws_layout& L, int bb, int k) { return I.W[(size_t)bb * L.NC + k]; }
-
 // one wave: rank block kb of image b.  Besides the attribution it evaluates, in parallel over all rank blocks, the overlap of
 // every rank with the leader that removed it (plead[k], groups_kernel's membership test) -- as a prologue of groups_kernel these
 // N dependent gathers ran on ONE CU (50 us of its 180 at N=16384).  `src`: see kFromMatrix / kFromBoxes / kFromRecords.

@@ -124,8 +124,9 @@ __device__ __forceinline__ void one_launch_bits_from_matrix(const float* __restr
 // The table straight from the BOXES (gnms_forward_with_iou2d's one launch: the matrix is an output there).  In rank space nothing has to be
 // permuted: task (tb, bb <= tb) -- its number IS the table's pair index -- holds the 64 target boxes of rank block tb in its lanes, walks
 // the sources of block bb (wave-uniform, broadcast with v_readlane) and a lane's bits are its word, stored coalesced.  The decision is
-// bitmask_boxes_body's, operation for operation (sign of fma(-thr, uni, inter) outside a guard band of 8 ulp, the IEEE division inside it
-// and for boxes without a positive finite area), i.e. bit for bit `!(iou <= thr)` of the matrix the writers of the same launch store.
+// bitmask_boxes_body's scalar row -- the same iou_row_terms and iou_guard_band (gnms_device.h): the sign of fma(-thr, uni, inter) outside the
+// guard band, the IEEE division inside it and for boxes without a positive finite area --, i.e. bit for bit `!(iou <= thr)` of the matrix
+// the writers of the same launch store.
 // Workgroup w of an image: tasks [w * tpw, (w + 1) * tpw), each on 16 / tpw waves that share the 64 sources; tpw in {1, 2, 4, 8, 16}.
 __device__ __forceinline__ void one_launch_bits_from_boxes(int N, const int* __restrict__ counts, const float thr, char* ws, gnms_ws_layout L,
                                                            const int b, const int w, const int tpw, const unsigned tag, const int nsort) {
@@ -152,7 +153,7 @@ __device__ __forceinline__ void one_launch_bits_from_boxes(int N, const int* __r
         const float tarea = (tbx.z - tbx.x) * (tbx.w - tbx.y), sarea = (sbx.z - sbx.x) * (sbx.w - sbx.y);
         const bool targets_ok = __all((tarea > 0.0f) && (tarea < INFINITY));
         const u64 sources_ok = __ballot((sarea > 0.0f) && (sarea < INFINITY));
-        const float guard = fmaxf(fabsf(thr), 1.0f) * 9.6e-7f;                   // 8 ulp at the threshold's magnitude (bitmask_boxes_body)
+        const float guard = iou_guard_band(thr);
         const int spp = 64 / wpt, nsrc = min(64, n - bb * 64);
         const int s1 = min(nsrc, (part + 1) * spp);
         for (int s = part * spp; s < s1; ++s) {
@@ -161,11 +162,8 @@ __device__ __forceinline__ void one_launch_bits_from_boxes(int N, const int* __r
             const float ax2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sbx.z), s));
             const float ay2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sbx.w), s));
             const float aa = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sarea), s));
-            const float wd = fmaxf(gnms_iou3d::vmin_s(ax2, tbx.z) - gnms_iou3d::vmax_s(ax1, tbx.x), 0.0f);
-            const float ht = fmaxf(gnms_iou3d::vmin_s(ay2, tbx.w) - gnms_iou3d::vmax_s(ay1, tbx.y), 0.0f);
-            const float inter = wd * ht;
-            const float uni = (aa + tarea) - inter;
-            const float d = __builtin_fmaf(-thr, uni, inter);
+            float inter, uni, d;
+            iou_row_terms(ax1, ay1, ax2, ay2, aa, tbx, tarea, thr, inter, uni, d);
             const bool unsure = !(fabsf(d) > guard * uni);                       // also true for NaN
             bool bit;
             if (!(targets_ok && ((sources_ok >> s) & 1ull)) || __any(unsure)) bit = !(inter / uni <= thr);
@@ -192,7 +190,7 @@ __device__ __forceinline__ void one_launch_bits_from_boxes(int N, const int* __r
 // x-rank 64 v .. 64 v + 63 as its lanes (N <= 1024: sixteen waves cover every source), rows that do not reach into the wave's hull are skipped,
 // and a set pair -- a few per row -- goes to bit (source rank & 63) of word (target row, source rank >> 6) of an LDS table by one LDS atomic;
 // the words of source blocks <= tb then leave as the table image's (tb, bb) entries.  Needs the x sort as a second sort role of the launch
-// (sort_count_body role 1: xidx, xbox).  The decision is bitmask_boxes_body's general row, operation for operation.
+// (sort_count_body role 1: xidx, xbox).  The decision is bitmask_boxes_body's scalar row (iou_row_terms, iou_guard_band).
 __device__ __forceinline__ void one_launch_bits_from_boxes_x(int N, const int* __restrict__ counts, const float thr, char* ws, gnms_ws_layout L,
                                                              const int b, const int tb, const unsigned tag, const int nsort) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -222,7 +220,7 @@ __device__ __forceinline__ void one_launch_bits_from_boxes_x(int N, const int* _
         const u64 rows_ok = __ballot(row_fine);
         const bool reaches = (rb.z > hx0) && (rb.x < hx1) && (rb.w > hy0) && (rb.y < hy1);
         u64 todo = __ballot((lane < nrows) && (!(cull && row_fine) || reaches));
-        const float guard = fmaxf(fabsf(thr), 1.0f) * 9.6e-7f;                   // 8 ulp at the threshold's magnitude (bitmask_boxes_body)
+        const float guard = iou_guard_band(thr);
         const bool mine = (p < n) && ((crank >> 6) <= tb);                       // a source the table holds for this target block
         while (todo) {                                                           // wave-uniform loop over the surviving rows
             const int r = __builtin_ctzll(todo);
@@ -232,11 +230,8 @@ __device__ __forceinline__ void one_launch_bits_from_boxes_x(int N, const int* _
             const float ax2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rb.z), r));
             const float ay2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rb.w), r));
             const float aa = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rarea), r));
-            const float w = fmaxf(gnms_iou3d::vmin_s(ax2, cb.z) - gnms_iou3d::vmax_s(ax1, cb.x), 0.0f);
-            const float h = fmaxf(gnms_iou3d::vmin_s(ay2, cb.w) - gnms_iou3d::vmax_s(ay1, cb.y), 0.0f);
-            const float inter = w * h;
-            const float uni = (aa + carea) - inter;
-            const float d = __builtin_fmaf(-thr, uni, inter);
+            float inter, uni, d;
+            iou_row_terms(ax1, ay1, ax2, ay2, aa, cb, carea, thr, inter, uni, d);
             const bool unsure = !(fabsf(d) > guard * uni);                       // also true for NaN
             bool bit;
             if (!(cols_ok && ((rows_ok >> r) & 1ull)) || __any(unsure)) bit = !(inter / uni <= thr);

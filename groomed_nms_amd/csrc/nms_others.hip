@@ -15,7 +15,7 @@
 // reference's own test feeds, test/test_differentiable_nms_forward.py:111; fp32 for float32 input), the union `float(...)`-ed to a
 // double (:78), overlap, weight and the product weight * score in double, rounded to T on the store (:93) -- NumPy 1.14 scalar
 // promotion, the reference's pinned version (dependencies/conda.txt); for float64 input (the tested case) every step is fp64.
-#include "nms_kernels.h"
+#include "gnms_device.h"
 
 namespace {
 

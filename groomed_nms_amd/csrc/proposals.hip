@@ -10,7 +10,7 @@
 #include <algorithm>
 #include <map>
 #include <mutex>
-#include "nms_kernels.h"
+#include "gnms_device.h"
 #include "bbox_decode.h"
 
 namespace {

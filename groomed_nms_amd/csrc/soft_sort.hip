@@ -15,7 +15,7 @@
 #include <mutex>
 #include <hipblaslt/hipblaslt.h>   // (types and enumerators only: the entry points are resolved with dlsym, below)
 #include <type_traits>
-#include "nms_kernels.h"
+#include "nms_sort_kernels.h"
 
 namespace {
 

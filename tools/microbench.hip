@@ -11,19 +11,6 @@ using namespace gnms;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
 
 template <int E>
-__global__ __launch_bounds__(1024) void sort_only_bitonic_kernel(const u64* in, u64* out, int P) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* keys = reinterpret_cast<u64*>(smem);
-    u64 r[E];
-    const u64* src = in + (size_t)blockIdx.x * P;
-#pragma unroll
-    for (int e = 0; e < E; ++e) r[e] = src[threadIdx.x * E + e];
-    block_sort_bitonic<E, u64>(r, keys, P);
-#pragma unroll
-    for (int e = 0; e < E; ++e) out[(size_t)blockIdx.x * P + threadIdx.x * E + e] = r[e];
-}
-
-template <int E>
 __global__ __launch_bounds__(1024) void sort_only_kernel(const u64* in, u64* out, int P) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     u64* keys = reinterpret_cast<u64*>(smem);
@@ -139,11 +126,11 @@ int main(int argc, char** argv) {
     printf("forward (all)           %8.1f us\n", time_us([&] { gnms_forward(d_scores, d_iou, B, N, N, nullptr, &P, d_prob, nullptr, nullptr, nullptr, nullptr, nullptr, ws, wsb, nullptr); }));
     const size_t llds = leaders_lds_size(L.NB);
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(leaders_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds));
-    printf("leaders                 %8.1f us\n", time_us([&] { leaders_kernel<<<B, 1024, llds>>>(N, nullptr, ws, L); }));
+    printf("leaders                 %8.1f us\n", time_us([&] { leaders_kernel<<<B, 1024, llds>>>(N, nullptr, ws, L, 0, B, 1); }));
 #ifdef GNMS_TIMING
     {
         long long z[8] = {0}; CK(hipMemcpy(img_ptrs(ws, L, 0).gx, z, sizeof(z), hipMemcpyHostToDevice));
-        leaders_kernel<<<B, 1024, llds>>>(N, nullptr, ws, L); CK(hipDeviceSynchronize());
+        leaders_kernel<<<B, 1024, llds>>>(N, nullptr, ws, L, 0, B, 1); CK(hipDeviceSynchronize());
         CK(hipMemcpy(z, img_ptrs(ws, L, 0).gx, sizeof(z), hipMemcpyDeviceToHost));
         printf("  leaders phases (cycles, wave0): prologue %lld | resolve %lld | barrierA %lld | push+book %lld | barrierB %lld\n", z[0], z[1], z[2], z[3], z[4]);
     }
@@ -151,14 +138,14 @@ int main(int argc, char** argv) {
     {
         const bool vec = true;
         dim3 gm((N + kMaskWaves * 256 - 1) / (kMaskWaves * 256), L.NB, B);
-        float tb = time_us([&] { bitmask_kernel<true><<<gm, kMaskWaves * 64>>>(d_iou, N, N, nullptr, 0.4f, ws, L); });
-        float tbl = time_us([&] { bitmask_kernel<true><<<gm, kMaskWaves * 64>>>(d_iou, N, N, nullptr, 0.4f, ws, L); leaders_kernel<<<B, 1024, llds>>>(N, nullptr, ws, L); });
+        float tb = time_us([&] { bitmask_kernel<true><<<gm, kMaskWaves * 64>>>(d_iou, N, N, nullptr, 0.4f, ws, L, 0, 0); });
+        float tbl = time_us([&] { bitmask_kernel<true><<<gm, kMaskWaves * 64>>>(d_iou, N, N, nullptr, 0.4f, ws, L, 0, 0); leaders_kernel<<<B, 1024, llds>>>(N, nullptr, ws, L, 0, B, 1); });
         printf("bitmask                 %8.1f us ; bitmask+leaders %8.1f us -> leaders cold %8.1f us\n", tb, tbl, tbl - tb);
         (void)vec;
 #ifdef GNMS_TIMING
         long long z[8] = {0}; CK(hipMemcpy(img_ptrs(ws, L, 0).gx, z, sizeof(z), hipMemcpyHostToDevice));
-        bitmask_kernel<true><<<gm, kMaskWaves * 64>>>(d_iou, N, N, nullptr, 0.4f, ws, L);
-        leaders_kernel<<<B, 1024, llds>>>(N, nullptr, ws, L); CK(hipDeviceSynchronize());
+        bitmask_kernel<true><<<gm, kMaskWaves * 64>>>(d_iou, N, N, nullptr, 0.4f, ws, L, 0, 0);
+        leaders_kernel<<<B, 1024, llds>>>(N, nullptr, ws, L, 0, B, 1); CK(hipDeviceSynchronize());
         CK(hipMemcpy(z, img_ptrs(ws, L, 0).gx, sizeof(z), hipMemcpyDeviceToHost));
         printf("  COLD leaders phases (cycles, wave0): prologue %lld | resolve %lld | barrierA %lld | push+book %lld | barrierB %lld\n", z[0], z[1], z[2], z[3], z[4]);
 #endif
@@ -171,22 +158,22 @@ int main(int argc, char** argv) {
         printf("bitmask_boxes rcp    u4 %8.1f us\n", time_us([&] { bitmask_boxes_exp<1, 4><<<gb, 256>>>(d_boxes, N, 0.4f, ws, L); }));
         printf("bitmask_boxes xmul   u4 %8.1f us\n", time_us([&] { bitmask_boxes_exp<2, 4><<<gb, 256>>>(d_boxes, N, 0.4f, ws, L); }));
         // restore W for the kernels below
-        bitmask_kernel<true><<<dim3((N + kMaskWaves * 256 - 1) / (kMaskWaves * 256), L.NB, B), kMaskWaves * 64>>>(d_iou, N, N, nullptr, 0.4f, ws, L);
+        bitmask_kernel<true><<<dim3((N + kMaskWaves * 256 - 1) / (kMaskWaves * 256), L.NB, B), kMaskWaves * 64>>>(d_iou, N, N, nullptr, 0.4f, ws, L, 0, 0);
     }
-    printf("attribute               %8.1f us\n", time_us([&] { attribute_kernel<false><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, ws, L); }));
+    printf("attribute               %8.1f us\n", time_us([&] { attribute_kernel<kFromMatrix><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, P.nms_threshold, ws, L, 0); }));
     if (P2 == 4096) {
-        printf("sort_scores<4>          %8.1f us\n", time_us([&] { sort_scores_kernel<4><<<B, T, sort_lds>>>(d_scores, N, nullptr, ws, L, P2, nullptr, nullptr); }));
+        printf("sort_scores<4>          %8.1f us\n", time_us([&] { sort_scores_kernel<4><<<B, T, sort_lds>>>(d_scores, N, nullptr, ws, L, P2, nullptr, nullptr, 0); }));
         // groups_kernel consumes the leader ordinals attribute_kernel leaves in gpos (and overwrites gpos): time the pair
         {
-            const float ta = time_us([&] { attribute_kernel<false><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, ws, L); });
-            const float tag = time_us([&] { attribute_kernel<false><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, ws, L); groups_kernel<4, false><<<B, T, sort_lds>>>(d_iou, N, N, nullptr, P, ws, L, P2); });
+            const float ta = time_us([&] { attribute_kernel<kFromMatrix><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, P.nms_threshold, ws, L, 0); });
+            const float tag = time_us([&] { attribute_kernel<kFromMatrix><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, P.nms_threshold, ws, L, 0); groups_kernel<4, kFromMatrix><<<B, T, sort_lds>>>(d_iou, N, N, nullptr, P, ws, L, P2); });
             printf("groups<4>               %8.1f us (attribute + groups %.1f)\n", tag - ta, tag);
         }
 #ifdef GNMS_TIMING
         {
             long long z[16] = {0}; CK(hipMemcpy(img_ptrs(ws, L, 0).gx, z, sizeof(z), hipMemcpyHostToDevice));
-            attribute_kernel<false><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, ws, L);
-            groups_kernel<4, false><<<B, T, sort_lds>>>(d_iou, N, N, nullptr, P, ws, L, P2); CK(hipDeviceSynchronize());
+            attribute_kernel<kFromMatrix><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, P.nms_threshold, ws, L, 0);
+            groups_kernel<4, kFromMatrix><<<B, T, sort_lds>>>(d_iou, N, N, nullptr, P, ws, L, P2); CK(hipDeviceSynchronize());
             CK(hipMemcpy(z, img_ptrs(ws, L, 0).gx, sizeof(z), hipMemcpyDeviceToHost));
             printf("  groups phases (cycles, thread0): keys %lld | sort %lld | runs %lld | rescoring %lld\n", z[8], z[9], z[10], z[11]);
         }
@@ -205,13 +192,6 @@ int main(int argc, char** argv) {
         u64 *din, *dout; CK(hipMalloc(&din, hk.size() * 8)); CK(hipMalloc(&dout, hk.size() * 8));
         CK(hipMemcpy(din, hk.data(), hk.size() * 8, hipMemcpyHostToDevice));
         printf("block_sort<4> only      %8.1f us\n", time_us([&] { sort_only_kernel<4><<<B, 1024, sort_lds>>>(din, dout, P2); }));
-#ifdef GNMS_TIMING
-        { long long z[4] = {0}; CK(hipMemcpyToSymbol(HIP_SYMBOL(g_sort_ticks), z, sizeof(z)));
-          sort_only_kernel<4><<<B, 1024, sort_lds>>>(din, dout, P2); CK(hipDeviceSynchronize());
-          CK(hipMemcpyFromSymbol(z, HIP_SYMBOL(g_sort_ticks), sizeof(z)));
-          printf("  block_sort<4,u64> cycles: LDS stages %lld | shuffle stages %lld | register stages %lld | final %lld\n", z[0], z[1], z[2], z[3]); }
-#endif
-        printf("bitonic<4> only         %8.1f us\n", time_us([&] { sort_only_bitonic_kernel<4><<<B, 1024, sort_lds>>>(din, dout, P2); }));
         printf("block_sort<8> only      %8.1f us\n", time_us([&] { sort_only_kernel<8><<<B, 512, sort_lds>>>(din, dout, P2); }));
         printf("block_sort<16> only     %8.1f us\n", time_us([&] { sort_only_kernel<16><<<B, 256, sort_lds>>>(din, dout, P2); }));
         std::vector<u64> ho(hk.size()); CK(hipMemcpy(ho.data(), dout, ho.size() * 8, hipMemcpyDeviceToHost));
@@ -222,20 +202,20 @@ int main(int argc, char** argv) {
         long long* d_valid; CK(hipMalloc(&d_valid, (size_t)B * N * 8 * 2));
         int* d_nv; CK(hipMalloc(&d_nv, B * 8));
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(sort_scores_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
-        CK(hipFuncSetAttribute(reinterpret_cast<const void*>(groups_kernel<16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
+        CK(hipFuncSetAttribute(reinterpret_cast<const void*>(groups_kernel<16, kFromMatrix>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
-        printf("sort_scores<16>         %8.1f us\n", time_us([&] { sort_scores_kernel<16><<<B, T, sort_lds>>>(d_scores, N, nullptr, ws, L, P2, nullptr, nullptr); }));
+        printf("sort_scores<16>         %8.1f us\n", time_us([&] { sort_scores_kernel<16><<<B, T, sort_lds>>>(d_scores, N, nullptr, ws, L, P2, nullptr, nullptr, 0); }));
         {
-            const float ta = time_us([&] { attribute_kernel<false><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, ws, L); });
-            const float tag = time_us([&] { attribute_kernel<false><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, ws, L); groups_kernel<16, false><<<B, T, sort_lds>>>(d_iou, N, N, nullptr, P, ws, L, P2); });
+            const float ta = time_us([&] { attribute_kernel<kFromMatrix><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, P.nms_threshold, ws, L, 0); });
+            const float tag = time_us([&] { attribute_kernel<kFromMatrix><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, P.nms_threshold, ws, L, 0); groups_kernel<16, kFromMatrix><<<B, T, sort_lds>>>(d_iou, N, N, nullptr, P, ws, L, P2); });
             printf("groups<16>              %8.1f us (attribute + groups %.1f)\n", tag - ta, tag);
         }
         printf("finalize<16>            %8.1f us\n", time_us([&] { finalize_kernel<16><<<B, T, sort_lds>>>(N, nullptr, P, ws, L, P2, d_prob, d_valid, d_valid + (size_t)B * N, d_nv, d_nv + B); }));
 #ifdef GNMS_TIMING
         {
             long long z[16] = {0}; CK(hipMemcpy(img_ptrs(ws, L, 0).gx, z, sizeof(z), hipMemcpyHostToDevice));
-            attribute_kernel<false><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, ws, L);
-            groups_kernel<16, false><<<B, T, sort_lds>>>(d_iou, N, N, nullptr, P, ws, L, P2);
+            attribute_kernel<kFromMatrix><<<dim3(L.NB, B), 64>>>(d_iou, (long)N, N, nullptr, P.nms_threshold, ws, L, 0);
+            groups_kernel<16, kFromMatrix><<<B, T, sort_lds>>>(d_iou, N, N, nullptr, P, ws, L, P2);
             finalize_kernel<16><<<B, T, sort_lds>>>(N, nullptr, P, ws, L, P2, d_prob, d_valid, d_valid + (size_t)B * N, d_nv, d_nv + B); CK(hipDeviceSynchronize());
             CK(hipMemcpy(z, img_ptrs(ws, L, 0).gx, sizeof(z), hipMemcpyDeviceToHost));
             printf("  groups phases (cycles, thread0): keys %lld | sort %lld | runs %lld | rescoring %lld\n", z[8], z[9], z[10], z[11]);

@@ -1,5 +1,5 @@
 """Developer tool: phase breakdown (s_memtime ticks of thread 0 of image 0) of the per-image kernels.  Needs a build with
-GNMS_EXTRA_FLAGS=-DGNMS_TIMING (python -m groomed_nms_amd.build --force); slots are the GNMS_TACC(n) markers in nms_kernels.h."""
+GNMS_EXTRA_FLAGS=-DGNMS_TIMING (python -m groomed_nms_amd.build --force); slots are the GNMS_TACC(n) markers in nms_scan_kernels.h (the leader scan) and nms_kernels.h."""
 import argparse
 import ctypes
 import os
