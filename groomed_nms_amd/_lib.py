@@ -68,6 +68,8 @@ _SIGNATURES = {
     "gnms_profile_bitmask_boxes": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_float, c_vp, ctypes.c_size_t, c_vp]),
     "gnms_profile_sorts": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                           c_vp, ctypes.c_size_t, c_vp]),
+    "gnms_profile_sort_paths": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_vp, ctypes.POINTER(ctypes.c_int32), c_vp, ctypes.c_size_t, c_vp]),
+    "gnms_profile_set_hist_cap": (ctypes.c_int, [ctypes.c_int]),
     "gnms_profile_events": (ctypes.c_int, [ctypes.c_int]),
     "gnms_profile_collect": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),
     "gnms_profile_write_kernel_name": (ctypes.c_char_p, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),

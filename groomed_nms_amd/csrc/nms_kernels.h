@@ -31,7 +31,7 @@
 namespace gnms {
 namespace {   // internal linkage: the header is included by several translation units
 
-// K1's two non-template kernels (bodies and their description: nms_sort_kernels.h)
+// K1's non-template kernels (bodies and their description: nms_sort_kernels.h)
 __global__ __launch_bounds__(1024) void sort_runs_kernel(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
                                                          const int* __restrict__ counts, char* ws, gnms_ws_layout L, int P, int mode3d) {
     sort_runs_body(scores, boxes, N, counts, ws, L, P, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, mode3d);
@@ -41,6 +41,12 @@ __global__ __launch_bounds__(1024) void sort_ranked_runs_kernel(const float* __r
                                                                 const int* __restrict__ counts, char* ws, gnms_ws_layout L,
                                                                 long long* __restrict__ order_out, int mode3d) {
     sort_ranked_runs_body(scores, boxes, N, counts, ws, L, order_out, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, mode3d);
+}
+
+__global__ __launch_bounds__(1024) void sort_hist_rank_kernel(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
+                                                              const int* __restrict__ counts, char* ws, gnms_ws_layout L,
+                                                              long long* __restrict__ order_out, int mode3d, int cap) {
+    sort_hist_rank_body(scores, boxes, N, counts, ws, L, order_out, cap, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, mode3d);
 }
 
 // ------------------------------------------------------------------------------------------------

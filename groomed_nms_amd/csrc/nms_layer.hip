@@ -1120,44 +1120,62 @@ int launch_bitmask_boxes(const LayerCall& c, const float* boxes) {
 // GNMS_RANK_SORT=0: 2048 < N <= 4096 sorts as runs + merge, two launches (developer / test switch, read once: the pair stays reachable for
 // A/B runs and the tests)
 bool rank_sort_enabled() { static const bool on = env_switch("GNMS_RANK_SORT", 1) != 0; return on; }
+// GNMS_HIST_SORT=0: the routing of round 8, no histogram sort (the same kind of switch)
+bool hist_sort_enabled() { static const bool on = env_switch("GNMS_HIST_SORT", 1) != 0; return on; }
+// keys in one bin from which on sort_hist_rank_kernel falls back to the run sort; gnms_profile_set_hist_cap moves it for the cap series
+std::atomic<int> g_hist_cap{kHistCap};
 
 // K1: stable descending score sort (+ the x-centre sort of the boxes when `boxes` is given).  Which kernels (measured per call in a replayed
-// graph of 20, MI355X, LABNOTES R8.1; W = workgroups of the ranked-runs launch = 16 * B * roles):
-//   N <= 2048; N <= 4096 with N / 64 * B * roles <= CUs (B <= 2 with boxes)   by counting, one launch (sort_count_kernel)
-//   2048 < N <= 4096 otherwise, while W <= CUs (B <= 8 with boxes, 16 without)  16 wave-sorted runs per workgroup, ranked in the same launch
-//                                                                               (sort_ranked_runs_kernel, round 8)
-//   everything else (N > 4096; W > CUs; GNMS_RANK_SORT=0)                       runs of 1024 + rank merge, two launches
+// graph of 20, MI355X, LABNOTES R8.1 and R13.3; G = workgroups of the counting sort = N / 64 * B * roles, W = workgroups of the one-launch sorts
+// of 2048 < N <= 4096 = 16 * B * roles):
+//   N <= 2048; N <= 4096 with G <= CUs / 2 (N = 4096: B = 1 with boxes, B <= 2 without)   by counting, one launch (sort_count_kernel)
+//   2048 < N <= 4096 otherwise, while W <= 3 CUs (B <= 24 with boxes, 48 without)       by histogram, one launch (sort_hist_rank_kernel, round 13)
+//   everything else (N > 4096; W > 3 CUs; GNMS_RANK_SORT=0)                             runs of 1024 + rank merge, two launches
+// GNMS_HIST_SORT=0 is the table of round 8: counting up to G <= CUs, then 16 wave-sorted runs per workgroup ranked in the same launch
+// (sort_ranked_runs_kernel) while W <= CUs, then runs + merge.
+// N = 4096, us per call, by histogram / ranked runs / runs + merge / counting: with boxes B = 1 7.45 / 9.8 / 12.4 / 7.42 (counting keeps it), B = 2
+// 7.5 / 10.0 / 12.4 / 10.0, B = 4 7.7 / 10.4 / 12.8, B = 8 8.0 / 11.5 / 13.4, B = 16 (two rounds of the machine) 10.7 / 16.3 / 15.0, B = 24 14.6 / 22.2 /
+// 16.4, B = 32 18.1 / 27.0 / 18.0 (runs + merge from here); scores alone B = 2 7.1 / 9.1 / 12.1 / 6.7 (counting), B = 4 7.2 / 9.3 / 12.2 / 9.3, B = 8
+// 7.4 / 9.6 / 12.4, B = 16 7.7 / 10.3 / 12.7, B = 32 10.4 / 15.2 / 13.9, B = 64 17.6 / 25.3 / 16.4; N = 2112 with boxes B = 2 6.3 / 9.3 / 12.1 / 6.6,
+// B = 3 6.4 / 9.4 / 12.3 / 6.8, B = 8 6.7 / 10.1 / 12.6; N = 3072 B = 8 7.4 / 10.6 / 13.2.
 // mode3d: 0 = `boxes` are 2D boxes (columns by x centre); >= 1 = pseudo boxes of cuboids whose records lie in the workspace (columns by
 // (z band, x centre) with that many bands; the sort also leaves the records in column order, ImgPtrs::xrec)
-// route (gnms_profile_sorts): 0 = the table above, 1 = runs + merge, 2 = ranked runs
+// route (gnms_profile_sorts): 0 = the table above, 1 = runs + merge, 2 = ranked runs, 3 = by histogram
 int launch_sorts(const LayerCall& c, const float* scores, const float* boxes, int mode3d = 0, int route = 0) {
     const int B = c.B, N = c.N, P2 = c.P2;
     int rc;
     const int roles = boxes ? 2 : 1;
+    const long cus = (long)gnms_device_cu_count();
+    const long one_launch_wgs = (long)kRankRuns * B * roles;
+    const bool one_launch = P2 == 4096 && rank_sort_enabled();
+    const bool hist = one_launch && hist_sort_enabled() && one_launch_wgs <= 3 * cus;
     // up to 2048 keys: by counting, N / 64 workgroups per image and role (sort_count_kernel)
-    // (... and up to 4096 keys where its N / 64 workgroups per image and role are ONE round of the machine -- B <= 2 with boxes: 256 compares
-    // per thread.  N = 4096 with boxes, us per call: B = 1 counting 7.3, ranked runs 9.7, runs + merge 12.4; B = 2 10.05 / 9.9 / 12.6 -- level
-    // with the ranked runs, so the counting sort keeps it; from two rounds on it loses, LABNOTES R5.6)
-    if (route == 0 && (N <= 2048 || (N <= 4096 && (long)B * ((N + 63) / 64) * roles <= (long)gnms_device_cu_count()))) {
+    // (... and up to 4096 keys while those workgroups fill at most half the machine, 256 compares per thread; on a full round the count takes
+    // 9.3-10.0 us and the histogram sort 7.2-7.5.  Without the histogram sort: while they are one round, level with the ranked runs, LABNOTES R5.6)
+    const long count_wgs = (long)B * ((N + 63) / 64) * roles;
+    if (route == 0 && (N <= 2048 || (N <= 4096 && (hist ? 2 * count_wgs : count_wgs) <= cus))) {
         const int NP = (N + 63) & ~63;
-        if (NP % 128 == 0 && (long)B * (NP / 32) * roles <= (long)gnms_device_cu_count())   // half the compares per thread while the grid is one round
+        if (NP % 128 == 0 && (long)B * (NP / 32) * roles <= cus)        // half the compares per thread while the grid is one round
             sort_count_kernel<32><<<dim3(NP / 32, B, roles), 1024, (size_t)NP * 8, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L, (long long*)c.order, mode3d);
         else
             sort_count_kernel<64><<<dim3(NP / 64, B, roles), 1024, (size_t)NP * 8, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L, (long long*)c.order, mode3d);
         GNMS_CHECK_LAUNCH();
         return GNMS_OK;
     }
-    // 2048 < N <= 4096 past that: the runs and their ranks in one launch, 16 workgroups per image and role -- while those are one round of the
-    // machine.  N = 4096, us per call, ranked runs / runs + merge: with boxes B = 4 10.3 / 12.8, B = 8 11.5 / 13.5, B = 16 (512 workgroups)
-    // 16.4 / 15.0; scores alone B = 8 9.5 / 12.4, B = 16 10.3 / 12.7, B = 32 (512 workgroups) 15.4 / 13.9; N = 2112 and 3072 at B = 8 with boxes
-    // 10.1 / 12.7 and 10.5 / 13.2.  Every workgroup repeats its image's run sort, so a second round costs more than the second launch saves.
-    if (route == 2 || (route == 0 && P2 == 4096 && rank_sort_enabled() && (long)kRankRuns * B * roles <= (long)gnms_device_cu_count())) {
+    // 2048 < N <= 4096 past that: one launch, 16 workgroups per image and role, each holding all keys of its image.  By histogram no workgroup
+    // sorts anything, and a second and third round of the machine still beat the second launch of runs + merge; the ranked runs repeat the
+    // image's run sort in every workgroup and are taken only while they are one round.
+    if (route == 2 || route == 3 || (route == 0 && one_launch && (hist || one_launch_wgs <= cus))) {
         if (P2 != 4096) {
-            gnms_set_error("launch_sorts: the ranked-runs sort takes 2048 < N <= 4096 (N=%d)", N);
+            gnms_set_error("launch_sorts: the %s sort takes 2048 < N <= 4096 (N=%d)", route == 3 ? "histogram" : "ranked-runs", N);
             return GNMS_ERR_UNSUPPORTED;
         }
-        sort_ranked_runs_kernel<<<dim3(kRankRuns, B, roles), 1024, (size_t)kRankRuns * kRankRunKeys * 8, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L,
-                                                                                                             (long long*)c.order, mode3d);
+        const dim3 grid(kRankRuns, B, roles);
+        const size_t lds = (size_t)kRankRuns * kRankRunKeys * 8;
+        if (route == 3 || (route == 0 && hist))
+            sort_hist_rank_kernel<<<grid, 1024, lds, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L, (long long*)c.order, mode3d, g_hist_cap.load());
+        else
+            sort_ranked_runs_kernel<<<grid, 1024, lds, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L, (long long*)c.order, mode3d);
         GNMS_CHECK_LAUNCH();
         return GNMS_OK;
     }
@@ -1863,7 +1881,7 @@ extern "C" int gnms_profile_sorts(const float* scores, const float* boxes, int B
     gnms_default_params(&P);
     int rc = check_common("gnms_profile_sorts", B, N, N, &P, workspace, workspace_bytes);
     if (rc) return rc;
-    GNMS_CHECK_ARG(route >= 0 && route <= 2, "gnms_profile_sorts: route %d (0 default, 1 runs + merge, 2 ranked runs)", route);
+    GNMS_CHECK_ARG(route >= 0 && route <= 3, "gnms_profile_sorts: route %d (0 default, 1 runs + merge, 2 ranked runs, 3 by histogram)", route);
     if (B == 0 || N == 0) return GNMS_OK;
     GNMS_CHECK_ARG(scores != nullptr, "gnms_profile_sorts: scores is NULL");
     const LayerCall c = make_call(B, N, counts, P, workspace, stream);
@@ -1874,6 +1892,30 @@ extern "C" int gnms_profile_sorts(const float* scores, const float* boxes, int B
         GNMS_CHECK_LAUNCH();
     }
     return GNMS_OK;
+}
+
+namespace {
+__global__ void export_sort_paths_kernel(char* ws, gnms_ws_layout L, int B, int32_t* __restrict__ paths) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * B) paths[i] = gnms::img_ptrs(ws, L, i >> 1).misc[gnms::kSortPathSlot + (i & 1)];
+}
+}  // namespace
+
+extern "C" int gnms_profile_sort_paths(int B, int N, int32_t* paths, int32_t* cap_out, void* workspace, size_t workspace_bytes, void* stream) {
+    gnms_params P;
+    gnms_default_params(&P);
+    int rc = check_common("gnms_profile_sort_paths", B, N, N, &P, workspace, workspace_bytes);
+    if (rc) return rc;
+    if (cap_out) *cap_out = g_hist_cap.load();
+    if (B == 0 || N == 0 || !paths) return GNMS_OK;
+    const LayerCall c = make_call(B, N, nullptr, P, workspace, stream);
+    export_sort_paths_kernel<<<gnms_div_up(2 * B, 64), 64, 0, c.st>>>(c.ws, c.L, B, paths);
+    GNMS_CHECK_LAUNCH();
+    return GNMS_OK;
+}
+
+extern "C" int gnms_profile_set_hist_cap(int cap) {
+    return g_hist_cap.exchange(cap < 0 ? gnms::kHistCap : std::min(cap, gnms::kHistCapMax));
 }
 
 // ------------------------------------------------------------------------------------------------

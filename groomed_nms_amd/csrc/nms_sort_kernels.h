@@ -1,10 +1,11 @@
 // nms_sort_kernels.h -- K1 of the GrooMeD-NMS layer: the stable descending argsort of the scores and, on the from-boxes paths, the
-// column order of the boxes (by x centre), as one workgroup per image (sort_scores_kernel), runs + merge, ranked runs, or by counting.
-// Everything here is a template or a __device__ body: a translation unit that includes this header (soft_sort.hip borrows
-// sort_scores_kernel<E>) gets only the kernels it instantiates.  The two non-template wrappers over sort_runs_body and
-// sort_ranked_runs_body, which only the layer launches, are in nms_kernels.h.
+// column order of the boxes (by x centre), as one workgroup per image (sort_scores_kernel), runs + merge, ranked runs, by histogram, or by
+// counting.  Everything here is a template or a __device__ body: a translation unit that includes this header (soft_sort.hip borrows
+// sort_scores_kernel<E>) gets only the kernels it instantiates.  The non-template wrappers over sort_runs_body, sort_ranked_runs_body and
+// sort_hist_rank_body, which only the layer launches, are in nms_kernels.h.
 #pragma once
 #include "gnms_device.h"
+#include "sort_bins.h"
 
 namespace gnms {
 namespace {   // internal linkage: the header is included by several translation units
@@ -26,13 +27,13 @@ __device__ __forceinline__ bool box_orders_plainly(const float4 v) {
 // (one SLOT of a wave tile) are a compact patch in x AND z and the rows far from it in either direction are skipped.  mode3d = 0: plain
 // 2D boxes by x centre; 1: cuboids, one band.  Key = band << 60 | x key << 28 | input index (N <= 16384): distinct, NaN x last.
 constexpr unsigned kColIdxMask = 0x0fffffffu;
+__device__ __forceinline__ unsigned column_band(const float4 v, int nbands, float zlo, float zscale) {
+    if (nbands <= 1) return 0u;
+    const float f = (v.w - zlo) * zscale;
+    return (f == f) ? (unsigned)fminf(fmaxf(f, 0.0f), (float)(nbands - 1)) : (unsigned)(nbands - 1);
+}
 __device__ __forceinline__ u64 column_key(const float4 v, int i, int nbands, float zlo, float zscale) {
-    unsigned band = 0u;
-    if (nbands > 1) {
-        const float f = (v.w - zlo) * zscale;
-        band = (f == f) ? (unsigned)fminf(fmaxf(f, 0.0f), (float)(nbands - 1)) : (unsigned)(nbands - 1);
-    }
-    return ((u64)band << 60) | ((u64)(~gnms_desc_key(v.x + v.z)) << 28) | (unsigned)i;
+    return ((u64)column_band(v, nbands, zlo, zscale) << 60) | ((u64)(~gnms_desc_key(v.x + v.z)) << 28) | (unsigned)i;
 }
 // range of z0 + z1 over the image's finite pseudo boxes -> (zlo, nbands / (zhi - zlo)); every thread of the workgroup returns the same pair
 // (min / max do not depend on the order), so every workgroup of an image bands alike
@@ -298,34 +299,52 @@ __device__ __forceinline__ void wave_sort_256(u64 (&r)[4]) {
     }
 }
 
-// (workgroup r of 16 of image b, role): grid (16, B, roles), 1024 threads, 4096 * 8 bytes of dynamic LDS; 2048 < N <= 4096
-__device__ __forceinline__ void sort_ranked_runs_body(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
-                                                      const int* __restrict__ counts, char* ws, gnms_ws_layout L,
-                                                      long long* __restrict__ order_out, const int r, const int b, const int role,
-                                                      const int mode3d = 0) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* keys = reinterpret_cast<u64*>(smem);                          // [16][256]: the image as 16 sorted runs (padding ~0: behind everything)
-    __shared__ int part[3][kRankRunKeys];                              // partial counts of quarters 1 .. 3
-    const int n = gnms_count(counts, b, N);
-    ImgPtrs I = img_ptrs(ws, L, b);
+// developer (tools/sort_ticks.py, timing build): the clock at the phase boundaries of wave 0 and wave 15 of workgroup 8 of image 0, per role,
+// the differences summed into xsol behind the bit-matrix kernel's slots.  Every tick drains the wave's memory operations first, so that a
+// phase is charged with the loads it issued.  path: 0 = sort_ranked_runs_kernel, 1 = sort_hist_rank_kernel by histogram, 2 = its fallback
+struct SortTicks {
+#ifdef GNMS_TIMING
+    long long v[10];
+    int n = 0;
+    __device__ __forceinline__ void tick() {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0);
+        v[n++] = (long long)__builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __device__ __forceinline__ void flush(const ImgPtrs& I, int b, int r, int role, int path) const {
+        if (b != 0 || r != 8 || (threadIdx.x != 0 && threadIdx.x != 960)) return;
+        long long* o = reinterpret_cast<long long*>(I.xsol) + 600 + path * 64 + role * 32 + (threadIdx.x ? 16 : 0);
+        for (int q = 1; q < n; ++q) o[q] += v[q] - v[q - 1];
+    }
+#else
+    __device__ __forceinline__ void tick() {}
+    __device__ __forceinline__ void flush(const ImgPtrs&, int, int, int, int) const {}
+#endif
+};
+
+// Thread t builds four keys of its image and role (padding ~0: behind everything) and keeps the value each is ordered by: the score, or the
+// x centre.  Role 0: keys 4t .. 4t+3, one float4 load; role 1: boxes 4t .. 4t+3, or with STRIDED boxes t + 1024 e, a wave's lanes then 16 bytes
+// apart instead of 64.  flag: role 0, workgroup 0 "the scores came in sorted"; role 1 "every box of mine is plain" (tested on the box the key
+// is made of, as sort_count_body does)
+template <bool STRIDED>
+__device__ __forceinline__ void sort_build_keys(const int role, const float* __restrict__ s, const float4* __restrict__ bx, const int n, const int N,
+                                                const int r, const int mode3d, const float zlo, const float zscale, u64 (&k)[4], float (&val)[4],
+                                                int& flag) {
     const int t = threadIdx.x;
-    const float* s = scores + (size_t)b * N;
-    const float4* bx = boxes ? reinterpret_cast<const float4*>(boxes) + (size_t)b * N : nullptr;
-    float zlo = 0.0f, zscale = 0.0f;
-    if (role == 1 && mode3d > 1) block_z_bands(bx, n, mode3d, &zlo, &zscale);
-    u64 k[4];
-    int flag = 1;                                                      // workgroup 0: role 0 "the scores came in sorted", role 1 "every box is plain"
+    flag = 1;
     if (role == 0) {
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) val[e] = 0.0f;
         if (4 * t + 3 < N && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
             const float4 q = reinterpret_cast<const float4*>(s)[t];
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+            val[0] = q.x; val[1] = q.y; val[2] = q.z; val[3] = q.w;
         } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) if (4 * t + e < n) v[e] = s[4 * t + e];
+            for (int e = 0; e < 4; ++e) if (4 * t + e < n) val[e] = s[4 * t + e];
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) k[e] = (4 * t + e < n) ? (((u64)gnms_desc_key(v[e]) << 32) | (unsigned)(4 * t + e)) : ~0ull;   // (sort_key_of)
+        for (int e = 0; e < 4; ++e) k[e] = (4 * t + e < n) ? (((u64)gnms_desc_key(val[e]) << 32) | (unsigned)(4 * t + e)) : ~0ull;   // (sort_key_of)
         if (r == 0) {                                                  // ascending keys in index order = the scores came in sorted
             const u64 next = (4 * t + 4 < n) ? sort_key_of(0, s, nullptr, 4 * t + 4, 0, 0.0f, 0.0f) : ~0ull;
             flag = (4 * t + 1 >= n || k[0] < k[1]) && (4 * t + 2 >= n || k[1] < k[2]) && (4 * t + 3 >= n || k[2] < k[3]) && (4 * t + 4 >= n || k[3] < next);
@@ -333,32 +352,75 @@ __device__ __forceinline__ void sort_ranked_runs_body(const float* __restrict__ 
     } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int i = 4 * t + e;
+            const int i = STRIDED ? t + 1024 * e : 4 * t + e;
             k[e] = ~0ull;
+            val[e] = 0.0f;
             if (i < n) {
                 const float4 v = bx[i];
                 k[e] = column_key(v, i, mode3d, zlo, zscale);
-                flag &= box_orders_plainly(v) ? 1 : 0;                 // (tested on the box the key is made of, as sort_count_body does)
+                val[e] = v.x + v.z;                                    // (column_key's x centre)
+                flag &= box_orders_plainly(v) ? 1 : 0;
             }
         }
     }
+}
+
+// what only one workgroup per image and role does: the flags (it holds every key, so it decides alone; all: role 0 "came in sorted", role 1
+// "every box is plain"), the counters, the call counter, the hand-off granules
+__device__ __forceinline__ void sort_image_flags(const ImgPtrs& I, const int role, const bool has_boxes, const int all) {
+    const int t = threadIdx.x;
+    if (role == 0) {
+        if (t < 8 && !(has_boxes && t == 6)) I.misc[t] = (t == 2) ? all : 0;               // ([6]: the x sort's)
+        if (t == 8) I.misc[8] = gnms_next_epoch(I.misc[8]);
+        for (int i = t; i < 17 * 32; i += 1024) I.gran[i] = 0ull;
+    } else if (t == 0) {
+        I.misc[6] = all ? 0 : 1;
+    }
+}
+
+// key of input index idx has rank `rank`: what it leaves behind (sv, bv: its score and box, requested before the rank was known)
+__device__ __forceinline__ void sort_store_ranked(const ImgPtrs& I, const int role, const int rank, const int idx, const float sv, const float4 bv,
+                                                  const bool has_boxes, long long* __restrict__ order_img, const int mode3d) {
+    if (role == 0) {
+        I.order[rank] = idx;
+        I.rankof[idx] = rank;
+        I.sscore[rank] = sv;
+        if (has_boxes) I.rbox[rank] = bv;                              // (the from-boxes layer: row boxes of the bit matrix)
+        if (order_img) order_img[rank] = idx;
+    } else {
+        column_store(I, rank, idx, bv, mode3d);
+    }
+}
+// padding ranks map to themselves (order is a permutation of [0, N)): workgroup r of 16 takes its share
+__device__ __forceinline__ void sort_store_padding(const ImgPtrs& I, const int n, const int N, const int r, long long* __restrict__ order_img) {
+    const int kp = n + r * 1024 + (int)threadIdx.x;
+    if (kp < N) {
+        I.order[kp] = kp; I.rankof[kp] = kp; I.sscore[kp] = 0.0f;
+        if (order_img) order_img[kp] = kp;
+    }
+}
+
+// The run sort and the ranks of workgroup r on the keys its threads hold: any split of the image's keys into 16 x 64 x 4 does.
+// housekeep: workgroup 0 also decides the flags here (sort_hist_rank_body has done that before it falls back to this)
+__device__ __forceinline__ void ranked_runs_finish(u64 (&k)[4], const int flag, const bool housekeep, SortTicks& T, const int path,
+                                                   const float* __restrict__ s, const float4* __restrict__ bx, const int N, const int n,
+                                                   const ImgPtrs& I, long long* __restrict__ order_img, const int r, const int b, const int role,
+                                                   const int mode3d) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    u64* keys = reinterpret_cast<u64*>(smem);                          // [16][256]: the image as 16 sorted runs (padding ~0: behind everything)
+    __shared__ int part[3][kRankRunKeys];                              // partial counts of quarters 1 .. 3
+    const int t = threadIdx.x;
     wave_sort_256(k);
+    T.tick();
 #pragma unroll
     for (int e = 0; e < 4; ++e) keys[4 * t + e] = k[e];
-    // what only one workgroup per image and role does: the flags (it holds every key, so it decides alone), the counters, the call counter,
-    // the hand-off granules
-    if (r == 0) {
+    if (housekeep && r == 0) {
         const int all = __syncthreads_and(flag);                       // (also: the runs are in LDS)
-        if (role == 0) {
-            if (t < 8 && !(boxes && t == 6)) I.misc[t] = (t == 2) ? all : 0;               // ([6]: the x sort's)
-            if (t == 8) I.misc[8] = gnms_next_epoch(I.misc[8]);
-            for (int i = t; i < 17 * 32; i += 1024) I.gran[i] = 0ull;
-        } else if (t == 0) {
-            I.misc[6] = all ? 0 : 1;
-        }
+        sort_image_flags(I, role, bx != nullptr, all);
     } else {
         __syncthreads();
     }
+    T.tick();
     const int key = t & (kRankRunKeys - 1), quarter = t >> 8;
     const u64 mine = keys[r * kRankRunKeys + key];
     const bool live = mine != ~0ull;
@@ -383,26 +445,168 @@ __device__ __forceinline__ void sort_ranked_runs_body(const float* __restrict__ 
         for (int j = 0; j < 4; ++j) cnt += (quarter * 4 + j == r) ? key : pos[j] + ((q4[j * kRankRunKeys + pos[j]] < mine) ? 1 : 0);
         if (quarter) part[quarter - 1][key] = cnt;
     }
+    T.tick();
     __syncthreads();
-    if (quarter == 0 && live) {
-        const int rank = cnt + part[0][key] + part[1][key] + part[2][key];
-        if (role == 0) {
-            I.order[rank] = idx;
-            I.rankof[idx] = rank;
-            I.sscore[rank] = sv;
-            if (bx) I.rbox[rank] = bv;                                 // (the from-boxes layer: row boxes of the bit matrix)
-            if (order_out) order_out[(size_t)b * N + rank] = idx;
-        } else {
-            column_store(I, rank, idx, bv, mode3d);
+    T.tick();
+    if (quarter == 0 && live) sort_store_ranked(I, role, cnt + part[0][key] + part[1][key] + part[2][key], idx, sv, bv, bx != nullptr, order_img, mode3d);
+    if (role == 0) sort_store_padding(I, n, N, r, order_img);
+    T.tick();
+    T.flush(I, b, r, role, path);
+}
+
+// (workgroup r of 16 of image b, role): grid (16, B, roles), 1024 threads, 4096 * 8 bytes of dynamic LDS; 2048 < N <= 4096
+__device__ __forceinline__ void sort_ranked_runs_body(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
+                                                      const int* __restrict__ counts, char* ws, gnms_ws_layout L,
+                                                      long long* __restrict__ order_out, const int r, const int b, const int role,
+                                                      const int mode3d = 0) {
+    SortTicks T;
+    T.tick();
+    const int n = gnms_count(counts, b, N);
+    ImgPtrs I = img_ptrs(ws, L, b);
+    const float* s = scores + (size_t)b * N;
+    const float4* bx = boxes ? reinterpret_cast<const float4*>(boxes) + (size_t)b * N : nullptr;
+    float zlo = 0.0f, zscale = 0.0f;
+    if (role == 1 && mode3d > 1) block_z_bands(bx, n, mode3d, &zlo, &zscale);
+    u64 k[4];
+    float val[4];
+    int flag;                                                          // workgroup 0: role 0 "the scores came in sorted", role 1 "every box is plain"
+    sort_build_keys<false>(role, s, bx, n, N, r, mode3d, zlo, zscale, k, val, flag);
+    T.tick();
+    ranked_runs_finish(k, flag, true, T, 0, s, bx, N, n, I, order_out ? order_out + (size_t)b * N : nullptr, r, b, role, mode3d);
+}
+
+// ------------------------------------------------------------------------------------------------
+// K1 for 2048 < N <= 4096 by HISTOGRAM (round 13): the same launch, grid and results as the ranked runs, without their sort.  There every one
+// of the 16 workgroups of an image and role sorts all sixteen runs in registers -- 36 compare-exchange stages on four 64-bit keys per lane,
+// 21 of them across lanes -- to rank one run.  A key's rank is the number of keys below it, and a histogram over a monotone function of the
+// key (sort_bins.h) gives nearly all of that: workgroup (r, image, role)
+//   builds every key of its image and role and reduces the finite minimum and maximum of the value they are ordered by (min / max do not
+//     depend on the order: the 16 workgroups bin alike, as with block_z_bands);
+//   bins each key, one LDS atomic per key on a histogram zeroed while the loads were in flight; the value the atomic returns is the key's
+//     slot in its bin;
+//   scans the bins (4 per thread, gnms_add_scan32 per wave, wave totals through LDS), the barrier of that scan deciding "some bin holds more
+//     than `cap` keys" on the way, and scatters the keys into bin order in LDS (the order inside a bin is whatever the atomics made it);
+//   ranks the bins that start in positions 256 r .. 256 r + 255 of that array: one thread per position counts the smaller keys of its key's
+//     bin, rank = bin start + count.  Keys are distinct, so the rank is exact whatever the slot order was.
+// Uniform scores and x centres put 2 keys into the average key's bin and at most 7-13 into any; values piled onto a few points (equal scores,
+// a detector's scores near zero, one far outlier stretching the range) fill single bins, and past `cap` keys in one bin the workgroup goes
+// on with the run sort on the keys it holds (ranked_runs_finish) -- for the whole image and role alike, the histogram being the same in all 16.
+// The stores land nearly contiguously per workgroup (ranks 256 r .. of the image) instead of scattered over the image.
+// ------------------------------------------------------------------------------------------------
+constexpr int kHistBins = 4096;
+constexpr int kHistCap = 96;             // keys in one bin past which the run sort takes over: the histogram still wins with 112 keys in EVERY bin, loses with 158 (LABNOTES R13.4)
+constexpr int kHistCapMax = 1024 - kRankRunKeys + 1;   // (the bins a workgroup ranks fit its 1024 threads)
+constexpr int kSortPathSlot = 10;        // misc[10 + role]: how the histogram sort went for this image and role, 1 = by histogram, 2 = fell back
+
+__device__ __forceinline__ void sort_hist_rank_body(const float* __restrict__ scores, const float* __restrict__ boxes, int N,
+                                                    const int* __restrict__ counts, char* ws, gnms_ws_layout L,
+                                                    long long* __restrict__ order_out, const int cap_arg, const int r, const int b, const int role,
+                                                    const int mode3d = 0) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    u64* keys = reinterpret_cast<u64*>(smem);                          // [4096] the image's keys in bin order
+    const int cap = cap_arg < kHistCapMax ? cap_arg : kHistCapMax;
+    __shared__ __attribute__((aligned(16))) unsigned hist[kHistBins];  // counts, then the bins' starts
+    __shared__ unsigned short binof[kRankRuns * kRankRunKeys];         // bin of the key at a position
+    __shared__ float red[2][16];
+    __shared__ unsigned wtot[16];
+    SortTicks T;
+    T.tick();
+    const int n = gnms_count(counts, b, N);
+    ImgPtrs I = img_ptrs(ws, L, b);
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const float* s = scores + (size_t)b * N;
+    const float4* bx = boxes ? reinterpret_cast<const float4*>(boxes) + (size_t)b * N : nullptr;
+    long long* order_img = order_out ? order_out + (size_t)b * N : nullptr;
+    reinterpret_cast<uint4*>(hist)[t] = make_uint4(0u, 0u, 0u, 0u);
+    float zlo = 0.0f, zscale = 0.0f;
+    if (role == 1 && mode3d > 1) block_z_bands(bx, n, mode3d, &zlo, &zscale);
+    u64 k[4];
+    float val[4];
+    int flag;
+    sort_build_keys<true>(role, s, bx, n, N, r, mode3d, zlo, zscale, k, val, flag);
+    float lo = INFINITY, hi = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (k[e] != ~0ull && fabsf(val[e]) < INFINITY) { lo = fminf(lo, val[e]); hi = fmaxf(hi, val[e]); }
+    lo = gnms_wave_min_f(lo); hi = gnms_wave_max_f(hi);
+    if (lane == 0) { red[0][wave] = lo; red[1][wave] = hi; }
+    if (r == 0) {
+        const int all = __syncthreads_and(flag);                       // (also: the histogram is zero, the waves' ranges are in LDS)
+        sort_image_flags(I, role, bx != nullptr, all);
+    } else {
+        __syncthreads();
+    }
+    lo = gnms_wave_min_f(lane < 16 ? red[0][lane] : INFINITY);
+    hi = gnms_wave_max_f(lane < 16 ? red[1][lane] : -INFINITY);
+    const unsigned bpb = (unsigned)kHistBins / (unsigned)((role == 1 && mode3d > 1) ? mode3d : 1);   // bins per z band
+    const float scale = hist_bin_scale(lo, hi, bpb);
+    T.tick();
+    unsigned bin[4], slot[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        bin[e] = 0u; slot[e] = 0u;
+        if (k[e] != ~0ull) {
+            bin[e] = (role == 0) ? hist_bin_desc(val[e], lo, scale, bpb) : (unsigned)(k[e] >> 60) * bpb + hist_bin_asc(val[e], lo, scale, bpb);
+            slot[e] = atomicAdd(&hist[bin[e]], 1u);
         }
     }
-    if (role == 0) {
-        const int kp = n + r * 1024 + t;                               // padding ranks map to themselves (order is a permutation of [0, N))
-        if (kp < N) {
-            I.order[kp] = kp; I.rankof[kp] = kp; I.sscore[kp] = 0.0f;
-            if (order_out) order_out[(size_t)b * N + kp] = kp;
+    __syncthreads();
+    T.tick();
+    const uint4 c = reinterpret_cast<const uint4*>(hist)[t];           // bins 4t .. 4t+3
+    const unsigned sum = c.x + c.y + c.z + c.w;
+    const unsigned inc = gnms_add_scan32(sum);
+    if (lane == 63) wtot[wave] = inc;
+    const unsigned most = max(max(c.x, c.y), max(c.z, c.w));
+    const int over = __syncthreads_or(most > (unsigned)cap);           // (also: the waves' totals are in LDS)
+    if (r == 0 && t == 0) I.misc[kSortPathSlot + role] = over ? 2 : 1;
+    if (over) {
+        ranked_runs_finish(k, flag, false, T, 2, s, bx, N, n, I, order_img, r, b, role, mode3d);
+        return;
+    }
+    {
+        const unsigned carry = (unsigned)__builtin_amdgcn_readlane((int)gnms_add_scan32((lane < wave) ? wtot[lane] : 0u), 63);
+        const unsigned ex = carry + inc - sum;
+        reinterpret_cast<uint4*>(hist)[t] = make_uint4(ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z);
+    }
+    __syncthreads();
+    T.tick();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (k[e] != ~0ull) {
+            const unsigned p = hist[bin[e]] + slot[e];                 // (< n: the bins' counts add up to n)
+            keys[p] = k[e];
+            binof[p] = (unsigned short)bin[e];
         }
     }
+    __syncthreads();
+    T.tick();
+    // Workgroup r ranks the bins that START in positions 256 r .. 256 r + 255 -- whole bins, not the positions themselves: which key of a bin
+    // stands at which of its positions is the atomics' order and differs from workgroup to workgroup, what is IN a bin does not.  Those bins
+    // end before position 256 r + 255 + cap, so thread t takes position 256 r + t and the first 255 + cap threads cover them (cap <= kHistCapMax).
+    const int p = r * kRankRunKeys + t;
+    bool ranked = false;
+    int idx = 0, rank = 0;
+    float sv = 0.0f;
+    float4 bv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (p < n && t < kRankRunKeys + cap - 1) {
+        const int mb = binof[p];
+        const int start = (int)hist[mb];
+        if (start >= r * kRankRunKeys && start < (r + 1) * kRankRunKeys) {
+            ranked = true;
+            const int end = (mb + 1 < kHistBins) ? (int)hist[mb + 1] : n;
+            const u64 mine = keys[p];
+            idx = (int)((unsigned)mine & (role == 0 ? 0xffffffffu : kColIdxMask));
+            if (role == 0) sv = s[idx];                                // (fetched by input index, under the count: sort_merge_body)
+            if (bx) bv = bx[idx];
+            rank = start;
+            for (int j = start; j < end; ++j) rank += (keys[j] < mine) ? 1 : 0;
+        }
+    }
+    T.tick();
+    if (ranked) sort_store_ranked(I, role, rank, idx, sv, bv, bx != nullptr, order_img, mode3d);
+    if (role == 0) sort_store_padding(I, n, N, r, order_img);
+    T.tick();
+    T.flush(I, b, r, role, 1);
 }
 
 // ------------------------------------------------------------------------------------------------

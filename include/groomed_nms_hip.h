@@ -245,13 +245,23 @@ int gnms_profile_bitmask_boxes(const float* boxes, int B, int N, const int32_t* 
                                size_t workspace_bytes, void* stream);
 
 /* profiling / test hook: only the sorts in front of the 2D layer (scores descending; with `boxes` [B][N][4], which may be NULL, also the
- * boxes by x centre), on a chosen route: 0 = what the layer takes, 1 = runs + merge (two launches), 2 = ranked runs (one launch,
- * 2048 < N <= 4096, GNMS_ERR_UNSUPPORTED elsewhere).  What the sorts leave in the workspace is copied into the caller's arrays, each
+ * boxes by x centre), on a chosen route: 0 = what the layer takes, 1 = runs + merge (two launches), 2 = ranked runs and 3 = by histogram
+ * (one launch each, 2048 < N <= 4096, GNMS_ERR_UNSUPPORTED elsewhere).  What the sorts leave in the workspace is copied into the caller's arrays, each
  * [B][N] (rbox, xbox: [B][N][4]) and each optional: order, rankof, sscore, and with boxes rbox, xidx, xbox (zeros behind an image's
  * count); flags [B][2] = "the scores came in sorted", "some box is not plain". */
 int gnms_profile_sorts(const float* scores, const float* boxes, int B, int N, const int32_t* counts, int route, int32_t* order,
                        int32_t* rankof, float* sscore, float* rbox, int32_t* xidx, float* xbox, int32_t* flags, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/* test hook: how the histogram sort (route 3, and route 0 where the layer takes it) went in the last call on this workspace.  paths: device
+ * array [B][2] (role 0 = scores, role 1 = boxes), 1 = ranked by histogram, 2 = some bin held more than the cap and the image and role fell
+ * back to the run sort; the slot is written by that kernel only, so after another route it holds what was there before.  cap_out (host,
+ * optional): the cap, keys in one bin, that later calls use. */
+int gnms_profile_sort_paths(int B, int N, int32_t* paths, int32_t* cap_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* developer hook (the cap series of tools/sort_routes.py): the histogram sort's cap for later calls, process-wide; 0 = every image falls
+ * back, 769 (the largest; more is clamped to it) = only bins past 769 keys do, negative = the built-in value.  Returns the previous cap. */
+int gnms_profile_set_hist_cap(int cap);
 
 /* Per-launch timing of the two HBM-bound launches inside whatever call sequence the caller runs (bench.py's roofline line).
  * gnms_profile_events(1) arms it: from then on every launch that writes an N x N overlap matrix (slot GNMS_PROF_MATRIX_WRITE:
