@@ -606,6 +606,54 @@ int gnms_cls_loss(const float* cls, const int64_t* labels, const float* labels_s
                   float* labels_weight, float* loss, float* dcls, double* acc, int32_t* stat_counts, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * What the training loss does with the sampled foreground (lib/loss/rpn_3d.py:1154-1407, fed by :206-233, :316-363, :477-579,
+ * :617-621): the 2D and 3D smooth-L1 terms, the axis / head cross entropies, the -log IoU term, the acceptance weighting, the
+ * uncertainty term with its running weight, the statistics and the gradients of the heads.  csrc/regression.hip, DESIGN.md 3.15.
+ * Configuration: decomp_alpha, orientation_bins = 0, infer_2d_from_3d = has_un = weigh_3D_regression_loss_by_gt_iou3d = False.
+ * Two stream-ordered launches, no allocation, no global atomics, no workgroup waits for another, nothing read back:
+ * graph-capturable with gnms_sample_anchors and gnms_cls_loss, and the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------------ */
+#define GNMS_REG_STATS 14          /* stats: bbox_2d, bbox_3d, un, iou_2d_los, cen, cen_dist_lt_0.2, z, rot, iou_2d, axis, head, conf,
+                                      total, the uncertainty weight in use */
+#define GNMS_REG_STAT_COUNTS 24    /* stat_counts: active anchors; finite elements of x, y, z, w, h, l, rot, axis, head before the
+                                      weighting [1..9]; of x .. rot as the term uses them [10..16]; finite IoUs, IoUs != 0, finite
+                                      -log IoU [17..19]; weighted, the IoU term exists [20..21]; 0 */
+/* Active anchors of image b: fg_index[b][0 .. fg_counts[b]) of gnms_sample_anchors (an entry outside [0, R) is passed over); counts
+ * [B][GNMS_SAMPLE_COUNT_COLS]: only images with counts[b][2] > 0 (the quota fg_num, :617) get an IoU, the others' IoUs are 0.
+ * Heads: bbox_2d [B][R][4]; bbox_3d [B][R][ld_bbox_3d >= 10] (x, y, z, w, h, l, rsin, rcos, axis, head; axis and head in [0, 1]);
+ * acceptance [B][R] or NULL.  Rows read where they lie, anchor r of image b at (b * R + r) * ld: transforms (>= 14 columns, normalised),
+ * raw_gt (>= 21), rois (>= 4), rois_3d (>= 11); rois_3d_cen [B][R][2]; p2 [B][p2_rows = 3 or 4][4] and scale_factor [B], float64, on
+ * the device.  means / stds: 13 values each ON THE HOST, read before the call returns.
+ * Terms (all means over the B images' active anchors together; per-anchor arithmetic in float64):
+ *   2D (:1163-1191)   bbox_2d_lambda * sum_k mean smooth_l1(bbox_2d[k] - transforms[k]); the prediction as the network gave it (the
+ *                     reference's has been denormalised in place by bbox_transform_inv; equal for means 0, stds 1)
+ *   3D (:1211-1373)   smooth-L1 of bbox_3d[0..5] against transforms[5..10], of rsin against transforms[12] where raw_gt[19] == 1, else
+ *                     of rcos against transforms[13]; binary cross entropy of axis / head against raw_gt[19] / raw_gt[20].  With
+ *                     bbox_un_dynamic, init = (sum of the seven means over finite elements) * bbox_3d_lambda + (the two cross
+ *                     entropies' means over finite elements) * bbox_axis_head_lambda before any weighting, and un_state = {n_frames,
+ *                     weight} (float64, on the device) is updated: n_frames 0 -> weight = init, n_frames = 1; else n_frames =
+ *                     min(100, n_frames + 1), weight = init / n_frames + weight * (n_frames - 1) / n_frames.  Every term is then
+ *                     multiplied by acceptance when use_acceptance, or when bbox_un_dynamic and the new weight > 0 (decided on the
+ *                     device).  Term = (sum of the seven means over finite elements + (plain means of the cross entropies) *
+ *                     bbox_axis_head_lambda) * bbox_3d_lambda.
+ *   un (:1375-1382)   weight > 0 (bbox_un_dynamic: un_state's, else bbox_un_lambda): mean(1 - acceptance) * weight
+ *   IoU (:1390-1405)  iou_2d_lambda != 0 and some active IoU != 0: iou_2d_lambda * mean over finite elements of -log IoU; IoU of
+ *                     core.py:522-529 (no + 1) between bbox_transform_inv of bbox_2d and of transforms[0..3], both from rois[b]
+ * Outputs, every element written: loss [1]; stats [GNMS_REG_STATS] float64; stat_counts [GNMS_REG_STAT_COUNTS]; d_bbox_2d,
+ * d_bbox_3d (rows of ld_bbox_3d), d_acceptance (with acceptance) = d loss / d head, 0 off the active set, in unread columns and on an
+ * element that an isfinite filter dropped.  No active anchor: loss 0, gradients 0, stats[0..12] NaN, un_state untouched.
+ * workspace: gnms_reg_loss_workspace_bytes(B, R) bytes, 8-byte aligned; d_bbox_2d 16-byte aligned. */
+size_t gnms_reg_loss_workspace_bytes(int B, int R);
+int gnms_reg_loss(const float* bbox_2d, const float* bbox_3d, int ld_bbox_3d, const float* acceptance, const float* transforms,
+                  int64_t ld_transforms, const float* raw_gt, int64_t ld_raw_gt, const float* rois, int ld_rois, const float* rois_3d,
+                  int ld_rois_3d, const float* rois_3d_cen, const double* p2, int p2_rows, const double* scale_factor,
+                  const int32_t* fg_index, const int32_t* fg_counts, const int32_t* counts, int B, int R, const double* means,
+                  const double* stds, double bbox_2d_lambda, double bbox_3d_lambda, double bbox_axis_head_lambda, double iou_2d_lambda,
+                  int use_acceptance, double bbox_un_lambda, int bbox_un_dynamic, double* un_state, float* loss, double* stats,
+                  int32_t* stat_counts, float* d_bbox_2d, float* d_bbox_3d, float* d_acceptance, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
