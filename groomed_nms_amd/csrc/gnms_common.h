@@ -120,6 +120,9 @@ static inline size_t gnms_align_up(size_t a, size_t b) { return (a + b - 1) / b 
 //                               without the order -> box gather)
 //     rec        float [N][12]  gnms_forward_with_iou3d: corner-AABB records of the cuboids (iou3d_pair.h)
 //     xrec       float [N][12]  the same records in the COLUMN order of the 3D bit-matrix kernel (z band, then x centre; written by the sort)
+//     plan       u64   [N]      masked groups, scores not pre-sorted: the BACKWARD PLAN, one entry per position p (plan_entry, nms_kernels.h;
+//                               read by bwd_plan_kernel).  [0, total): the members run after run as in gsorted, [total, n): the ranks in no
+//                               group, [n, N): padding.  Written by every builder of gsorted / gstart / glen (csr_build_body, groups_body)
 //     W          u64   [NB][NC] W[kb][k'] bit r set iff !(iou[order[64*kb+r]][order[k']] <= thr): the ranks of block kb that
 //                               rank k', were it a leader, takes out of `remaining` (:249-262).  Rank x rank space: the
 //                               bit-matrix kernel reads input columns and scatters each word to its rank position.
@@ -128,7 +131,7 @@ static inline size_t gnms_align_up(size_t a, size_t b) { return (a + b - 1) / b 
 struct gnms_ws_layout {
     int N, NB, NC;
     size_t off_order, off_sscore, off_rankof, off_rem, off_head, off_gpos, off_gsorted, off_gstart, off_glen, off_hlist, off_plead, off_pre,
-        off_r2, off_sidx, off_xsol, off_gx, off_leadc, off_leadr, off_leadw, off_leadpfx, off_misc, off_gran, off_xidx, off_xbox, off_rbox, off_rec, off_xrec, off_W;
+        off_r2, off_sidx, off_xsol, off_gx, off_leadc, off_leadr, off_leadw, off_leadpfx, off_misc, off_gran, off_xidx, off_xbox, off_rbox, off_rec, off_xrec, off_plan, off_W;
     size_t per_image;  // bytes
 };
 
@@ -153,6 +156,7 @@ static inline gnms_ws_layout gnms_make_layout(int N) {
     L.off_rbox = take(n4 * 4);
     L.off_rec = take(n4 * 12);
     L.off_xrec = take(n4 * 12);
+    L.off_plan = take(n4 * 2);
     {   // (up to one super-block the region also holds the image of the scan's triangular table, nms_one_launch.h: NB (NB + 1) / 2 pairs of 64 words)
         size_t wbytes = (size_t)(L.NB > 0 ? L.NB : 1) * (size_t)(L.NC > 0 ? L.NC : 4) * 8;
         const size_t tbytes = (size_t)L.NB * (L.NB + 1) / 2 * 64 * 8;

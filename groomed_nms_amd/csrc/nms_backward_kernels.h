@@ -85,6 +85,91 @@ __global__ __launch_bounds__(256) void bwd_masked_fused_kernel(const float* __re
     gs[I.order[k]] = (h >= 0) ? g : 0.0f;
 }
 
+// The same result from the BACKWARD PLAN the forward's run builders leave (plan_entry, nms_kernels.h): one thread per plan position.
+//   level 1: the plan entry (which rank sits here, where its gradient goes, its role);  level 2: pre, plead, dL/dprob of that rank, together.
+// bwd_masked_fused_kernel's head waves go misc[1] -> hlist -> gstart / glen -> gsorted -> pre / plead / dL/dprob, five dependent round trips.
+// A head's members are the FOLLOWING positions: their products come from the workgroup's LDS tile (256 positions + a halo of kPlanHalo, the
+// halo's products computed once more by this workgroup), subtracted one after the other in member order exactly as the readlane loop does.
+// The first 8 members per lane, every head of the wave at once; what a run has beyond them a wave takes 64 at a time.  A run longer than
+// the halo (group_size > kPlanHalo) is walked by the wave that holds its head, plan entry by plan entry: today's loop, one level shorter.
+// gx is stored only where bwd_masked_iou_kernel will read it (want_gx: dL/diou was asked for).
+// Indices out of a plan are clamped to the image: a workspace the forward never filled yields garbage, not a wild access.
+__device__ __forceinline__ void bwd_plan_terms(const float* __restrict__ gp, const ImgPtrs& I, int mk, float& g, float& prod) {
+    const float pre = I.pre[mk], pl = I.plead[mk], d = gp[mk];
+    g = (pre >= 0.0f && pre <= 1.0f) ? d : 0.0f;                     // (bwd_gx_of)
+    prod = pl * g;
+}
+
+__global__ __launch_bounds__(256) void bwd_plan_kernel(const float* __restrict__ grad_prob, int N, char* ws, gnms_ws_layout L,
+                                                       float* __restrict__ grad_scores, int want_gx) {
+    __shared__ float prods[256 + kPlanHalo];
+    const int b = blockIdx.y;
+    ImgPtrs I = img_ptrs(ws, L, b);
+    float* gs = grad_scores + (size_t)b * N;
+    const float* gp = grad_prob + (size_t)b * N;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int p = blockIdx.x * 256 + tid, ph = p + 256;
+    const unsigned last = (unsigned)(N - 1);
+    const bool halo = tid < kPlanHalo && ph < N;
+    const u64 ent = p < N ? I.plan[p] : ((u64)kPlanPadBit << 32);
+    const u64 eh = halo ? I.plan[ph] : 0ull;
+    const unsigned lo = (unsigned)ent, hi = (unsigned)(ent >> 32);
+    const int mk = (int)min(lo & 0x3fffu, last), dst = (int)min((lo >> 14) & 0x3fffu, last);
+    const unsigned role = (hi >> 29) & 3u;
+    const bool pad = (hi & kPlanPadBit) != 0u;
+    float g = 0.0f, prod = 0.0f, gh, prodh = 0.0f;
+    if (!pad && (role != kPlanZero || want_gx)) bwd_plan_terms(gp, I, mk, g, prod);
+    if (halo && ((unsigned)(eh >> 61) & 3u) == kPlanMember) bwd_plan_terms(gp, I, (int)min((unsigned)eh & 0x3fffu, last), gh, prodh);
+    prods[tid] = prod;
+    if (tid < kPlanHalo) prods[256 + tid] = prodh;
+    __syncthreads();
+    // (no thread leaves here: the loops below are a whole wave's work, whichever lanes hold heads.  Positions >= N carry the padding role.)
+    const bool live = p < N;
+    if (live && want_gx) I.gx[pad ? p : mk] = g;                     // (padding entries carry g = 0)
+    const bool head = role == kPlanHead;
+    const int rlen = (int)((hi >> 14) & 0x7fffu);
+    const int len = head ? min(rlen, kPlanHalo + 1) : rlen;
+    float acc = g;
+    if (head) {
+        const float* m = prods + tid + 1;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { const float v = m[u]; if (u + 1 < len) acc -= v; }
+    }
+    // runs of more than 9: the wave takes them one at a time, 64 products per LDS read, the chain by v_readlane + v_sub
+    u64 more = __ballot(head && len > 9);
+    while (more) {
+        const int src = __builtin_ctzll(more);
+        more &= more - 1ull;
+        const int hlen = __builtin_amdgcn_readlane(len, src), at = (tid & ~63) + src;
+        float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), src));
+        for (int base = 9; base < hlen; base += 64) {
+            const int t = base + lane;
+            const float v = t < hlen ? prods[at + t] : 0.0f;
+            const int cnt = min(64, hlen - base);
+            for (int u = 0; u < cnt; ++u) a -= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), u));
+        }
+        if (lane == src) acc = a;
+    }
+    // runs longer than the halo: their members' entries and terms from memory
+    u64 longs = __ballot(role == kPlanLongHead);
+    while (longs) {
+        const int src = __builtin_ctzll(longs);
+        longs &= longs - 1ull;
+        const int hp = __builtin_amdgcn_readlane(p, src);
+        const int hlen = min(__builtin_amdgcn_readlane(len, src), N - hp);
+        float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), src));
+        for (int base = 1; base < hlen; base += 64) {
+            const int t = base + lane;
+            float v = 0.0f, gm;
+            if (t < hlen) bwd_plan_terms(gp, I, (int)min((unsigned)I.plan[hp + t] & 0x3fffu, last), gm, v);
+            const int cnt = min(64, hlen - base);
+            for (int u = 0; u < cnt; ++u) a -= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), u));
+        }
+        if (lane == src) acc = a;
+    }
+    if (live) gs[pad ? p : dst] = role == kPlanZero ? 0.0f : acc;
+}
+
 __global__ __launch_bounds__(256) void bwd_masked_kernel(int N, const int* __restrict__ counts, gnms_params P, char* ws, gnms_ws_layout L,
                                                          float* __restrict__ grad_scores) {
     const int b = blockIdx.y;

@@ -951,6 +951,40 @@ __global__ __launch_bounds__(64) void attribute_kernel(const float* __restrict__
 // eight levels of them, this is four (rem / order / sscore -> the leader's order, score, ordinal -> the two boxes -> stores).
 constexpr int kBigGroupList = 16;     // groups above this size are also listed from the end of hlist (groups_body, solve_groups_kernel)
 
+// ------------------------------------------------------------------------------------------------
+// The BACKWARD PLAN (masked groups, scores not pre-sorted): what bwd_plan_kernel needs to know about position p, in one 8-byte entry, so
+// that the backward is "entry -> pre / plead / dL/dprob -> store" and nothing of head / glen / hlist / gstart / gsorted / order / misc is
+// on its path.  Positions follow the runs of gsorted: [0, total) the members run after run in rank order, [total, n) the ranks in no
+// group (and, inside a run K5 proper cut at the cap, the candidates cut off: same role), [n, N) padding.
+//   low word : rank mk (14 bits) | input index order[mk] << 14 (where dL/ds goes)
+//   high word: offset inside the run (14 bits) | run length << 14 (15 bits; on the run's first entry; <= N <= 16384) | role << 29 | padding << 31
+// Every builder of the runs writes it through plan_entry / plan_pad (or, where one thread knows the rank and another the run's length, the
+// two words separately: plan_lo / plan_hi), every call: the plan is never older than the runs beside it.
+// ------------------------------------------------------------------------------------------------
+constexpr int kPlanHalo = 128;              // members behind a head that bwd_plan_kernel sums from its tile of products (the default cap is 100 + 1)
+constexpr unsigned kPlanZero = 0u;          // in no group: dL/ds = 0
+constexpr unsigned kPlanMember = 1u;        // a member (or the head of a group of one): dL/ds = gx
+constexpr unsigned kPlanHead = 2u;          // head of a run of 2 .. kPlanHalo + 1 members: gx - sum of the following entries' products
+constexpr unsigned kPlanLongHead = 3u;      // head of a longer run: a whole wave walks the run
+constexpr unsigned kPlanPadBit = 1u << 31;  // (high word) position >= n: dL/ds[p] = 0, gx[p] = 0
+__device__ __forceinline__ unsigned plan_lo(int mk, int dst) { return (unsigned)mk | ((unsigned)dst << 14); }
+// rank `off` places behind the head of a run of `len` members (len counts on the head only); member = false: in no group
+__device__ __forceinline__ unsigned plan_hi(int off, int len, bool member) {
+    const unsigned role = !member ? kPlanZero : ((off != 0 || len <= 1) ? kPlanMember : (len <= kPlanHalo + 1 ? kPlanHead : kPlanLongHead));
+    return ((unsigned)off & 0x3fffu) | ((off == 0 && member ? (unsigned)len : 0u) << 14) | (role << 29);
+}
+__device__ __forceinline__ unsigned* plan_word(const ImgPtrs& I, int p, int hi) { return reinterpret_cast<unsigned*>(I.plan + p) + hi; }
+// (order through agent-scope loads: in the one launch the sort is a workgroup of the same launch)
+__device__ __forceinline__ int plan_dst(const ImgPtrs& I, int mk) { return coh_load(I.order + mk); }
+__device__ __forceinline__ void plan_entry(const ImgPtrs& I, int p, int mk, int dst, int off, int len, bool member) {
+    I.plan[p] = ((u64)plan_hi(off, len, member) << 32) | plan_lo(mk, dst);
+}
+// K5's sort key of a rank in no group: the leader bits all ones (no ordinal reaches them), the rank kept below them for the plan;
+// padding ranks (k >= n) sort behind them (the sort is stable)
+__device__ __forceinline__ unsigned key_no_group(int k, int n) { return k < n ? (0xffffc000u | (unsigned)k) : ~0u; }
+__device__ __forceinline__ bool key_is_no_group(unsigned key) { return (key >> 14) == 0x3ffffu; }
+__device__ __forceinline__ void plan_pad(const ImgPtrs& I, int p) { I.plan[p] = ((u64)kPlanPadBit << 32) | plan_lo(p, p); }
+
 template <int E, int SRC, bool FUSE = false>
 __device__ __forceinline__ void groups_body(const float* __restrict__ iou, int N, long ld, const int* __restrict__ counts,
                                             gnms_params P, char* ws, gnms_ws_layout L, int Ppow2, const int b) {
@@ -993,14 +1027,14 @@ __device__ __forceinline__ void groups_body(const float* __restrict__ iou, int N
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             const int k = e * (int)blockDim.x + (int)threadIdx.x;
-            keys[k] = (k < n && f_pl[e] > thr) ? (((unsigned)g[e] << 14) | (unsigned)k) : ~0u;   // strict > (:249)
+            keys[k] = (k < n && f_pl[e] > thr) ? (((unsigned)g[e] << 14) | (unsigned)k) : key_no_group(k, n);   // strict > (:249)
             info[k] = ~0u;
         }
     } else {
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const int k = e * (int)blockDim.x + (int)threadIdx.x;
-        unsigned key = ~0u;
+        unsigned key = key_no_group(k, n);
         if (k < n && I.plead[k] > thr) key = ((unsigned)I.gpos[k] << 14) | (unsigned)k;     // strict > (:249)
         keys[k] = key;
         info[k] = ~0u;
@@ -1021,6 +1055,7 @@ __device__ __forceinline__ void groups_body(const float* __restrict__ iou, int N
     //      t*E .. t*E+E-1; the start of each position's run comes from a max-scan of the run-start flags
     //      (registers -> wave shuffles -> 16 per-wave totals in LDS): no per-element search. ----
     const long long cap = (long long)P.group_size + 1;
+    const bool plan = P.mask_group_boxes && !P.presorted;             // the backward plan: for the route that reads it (bwd_plan_kernel)
     __shared__ int wave_last_start[16];
     {
         const int t = threadIdx.x, ln = t & 63, wv = t >> 6;
@@ -1031,7 +1066,7 @@ __device__ __forceinline__ void groups_body(const float* __restrict__ iou, int N
         for (int e = 0; e < E; ++e) {
             const int i = t * E + e;
             ky[e] = keys[i];
-            const bool valid = ky[e] != ~0u;
+            const bool valid = !key_is_no_group(ky[e]);
             const bool first = valid && (i == 0 || (keys[i - 1] >> 14) != (ky[e] >> 14));
             if (first) last = i;
             st[e] = last;
@@ -1045,29 +1080,42 @@ __device__ __forceinline__ void groups_body(const float* __restrict__ iou, int N
         int carry = -1;
         for (int w = 0; w < wv; ++w) carry = max(carry, wave_last_start[w]);
         const int before = max(excl, carry);
+        // the plan (see plan_entry): this thread knows which rank sits at its positions -> the low words, all gathers of order[] in one
+        // batch; the high word of a run's first entry comes from the thread that sees the run end
+        if (plan) {
+            int pdst[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) pdst[e] = (t * E + e < n) ? plan_dst(I, (int)(ky[e] & 0x3fffu)) : 0;
+#pragma unroll
+            for (int e = 0; e < E; ++e) if (t * E + e < n) *plan_word(I, t * E + e, 0) = plan_lo((int)(ky[e] & 0x3fffu), pdst[e]);
+        }
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             const int i = t * E + e;
             bool big_head = false;
             int hk = 0;
             if (i < n) {
-                if (ky[e] != ~0u) {
+                if (!key_is_no_group(ky[e])) {
                     const int k = (int)(ky[e] & 0x3fffu);
                     const int start = st[e] >= 0 ? st[e] : before;
                     const long long pos = i - start;
                     const unsigned hd = keys[start] & 0x3fffu;
                     if (pos < cap) info[k] = hd | ((unsigned)pos << 14);
-                    const bool lastofrun = (i + 1 >= n) || (keys[i + 1] == ~0u) || ((keys[i + 1] >> 14) != (ky[e] >> 14));
+                    if (plan && pos > 0) *plan_word(I, i, 1) = plan_hi((int)pos, 0, pos < cap);
+                    const bool lastofrun = (i + 1 >= n) || key_is_no_group(keys[i + 1]) || ((keys[i + 1] >> 14) != (ky[e] >> 14));
                     if (lastofrun) {                                  // the run's last element publishes the extent for the head
                         const long long len = pos + 1;
                         I.gstart[hd] = start;
                         I.glen[hd] = (int)(len < cap ? len : cap);
+                        if (plan) *plan_word(I, start, 1) = plan_hi(0, (int)(len < cap ? len : cap), true);
                         big_head = len > 1;
                         hk = (int)hd;
                         // groups of more than kBigGroupList members are listed a second time, from the END of hlist (misc[4] of them): the
                         // unmasked solves hand those to whole workgroups and everything smaller to single waves (nms_solve_kernels.h)
                         if ((len < cap ? len : cap) > kBigGroupList) I.hlist[N - 1 - atomicAdd(&I.misc[4], 1)] = hk;
                     }
+                } else if (plan) {
+                    *plan_word(I, i, 1) = plan_hi(0, 0, false);                      // in no group: the stable sort kept these in rank order behind the runs
                 }
             }
             // heads of multi-member groups go to hlist (one atomic per wave)
@@ -1081,7 +1129,8 @@ __device__ __forceinline__ void groups_body(const float* __restrict__ iou, int N
         }
     }
     // members in (group, rank) order, written lane-contiguously straight from the sorted keys
-    for (int i = threadIdx.x; i < n; i += blockDim.x) I.gsorted[i] = (keys[i] == ~0u) ? -1 : (int)(keys[i] & 0x3fffu);
+    if (plan) for (int i = n + (int)threadIdx.x; i < N; i += blockDim.x) plan_pad(I, i);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) I.gsorted[i] = key_is_no_group(keys[i]) ? -1 : (int)(keys[i] & 0x3fffu);
     __syncthreads();
     GNMS_TACC(10);
     // ---- phase 3 (lane-contiguous ranks k = e * blockDim + t: every load and store below is coalesced; with the thread-contiguous
@@ -1670,6 +1719,8 @@ __device__ __forceinline__ void csr_build_body(int N, const int* __restrict__ co
     int* fill = cnt + E * 1024;
     int* seg = fill + E * 1024;                                                      // the runs, members in arrival order
     int* startL = seg + E * 1024;
+    int* nogroup = startL + E * 1024;                                                // [64] ranks in no group per 64 ranks (E * 16 of them), then their prefix
+                                                                                     // (the dynamic LDS of every launch with a CSR workgroup is fast_tail_lds_size: 8 arrays)
     __shared__ int s_cnt[4];                                                         // [0] verdict, [1] multi-member heads, [2] big heads
     __shared__ int wave_tot[16];
     const int n = gnms_count(counts, b, N);
@@ -1693,15 +1744,24 @@ __device__ __forceinline__ void csr_build_body(int N, const int* __restrict__ co
     for (int i = tid; i < E * 1024; i += 1024) { cnt[i] = 0; fill[i] = 0; }
     __syncthreads();
     if (s_cnt[0] != 1) return;                                                       // K5 proper ran (or runs): it builds the runs itself
-    int hd[E];
+    int hd[E], pdst[E];                                                              // pdst: where rank k's gradient goes (the plan)
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const int k = e * 1024 + tid;
         hd[e] = (k < n) ? rem_load(I.head, k) : -1;
+        pdst[e] = (k < n) ? plan_dst(I, k) : 0;
     }
 #pragma unroll
-    for (int e = 0; e < E; ++e) if (hd[e] >= 0) atomicAdd(&cnt[hd[e]], 1);
+    for (int e = 0; e < E; ++e) {
+        if (hd[e] >= 0) atomicAdd(&cnt[hd[e]], 1);
+        const u64 loose = __ballot(e * 1024 + tid < n && hd[e] < 0);
+        if (lane == 0) nogroup[e * 16 + wave] = __builtin_popcountll(loose);
+    }
     __syncthreads();
+    if (wave == 0) {                                                                 // the plan's places for the ranks in no group: behind the runs, in rank order
+        const int v = lane < E * 16 ? nogroup[lane] : 0;
+        nogroup[lane] = (int)gnms_add_scan32((unsigned)v) - v;
+    }
     // run starts: exclusive scan of the counts over the ranks (thread t owns ranks t * E .. t * E + E - 1)
     int c[E], sum = 0;
 #pragma unroll
@@ -1736,6 +1796,7 @@ __device__ __forceinline__ void csr_build_body(int N, const int* __restrict__ co
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const int k = e * 1024 + tid;
+        const u64 loose = __ballot(k < n && hd[e] < 0);
         if (k >= N) continue;
         int pos = -1;
         if (hd[e] >= 0) {
@@ -1743,6 +1804,11 @@ __device__ __forceinline__ void csr_build_body(int N, const int* __restrict__ co
             pos = 0;
             for (int i = 0; i < len; ++i) pos += seg[st + i] < k ? 1 : 0;            // rank order inside the run, whatever order the atomics ran in
             I.gsorted[st + pos] = k;
+            plan_entry(I, st + pos, k, pdst[e], pos, len, true);
+        } else if (k < n) {
+            plan_entry(I, total + nogroup[e * 16 + wave] + __builtin_popcountll(loose & ((1ull << lane) - 1ull)), k, pdst[e], 0, 0, false);
+        } else {
+            plan_pad(I, k);
         }
         I.gpos[k] = pos;
         if (k >= n) { I.head[k] = -1; I.glen[k] = 0; }                               // padding ranks: in no group

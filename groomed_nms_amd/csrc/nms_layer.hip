@@ -1708,7 +1708,12 @@ extern "C" int gnms_backward(const float* grad_prob, const float* scores, const 
     if (grad_iou) GNMS_CHECK_HIP(hipMemsetAsync(grad_iou, 0, sizeof(float) * (size_t)B * N * ld, st));
     if (P.group_boxes && P.mask_group_boxes) {
         const int head_blocks = N >= 2048 ? 128 : gnms_div_up(N, 16);
-        if (fused_gx) {
+        // GNMS_BWD_PLAN=0: the backward that walks hlist / gstart / glen / gsorted instead of the forward's plan (A/B runs, the bit-for-bit test)
+        static const bool by_plan = env_switch("GNMS_BWD_PLAN", 1) != 0;
+        if (fused_gx && by_plan) {
+            bwd_plan_kernel<<<ge, 256, 0, st>>>(grad_prob, N, ws, L, grad_scores, grad_iou ? 1 : 0);
+            GNMS_CHECK_LAUNCH();
+        } else if (fused_gx) {
             bwd_masked_fused_kernel<<<dim3(ge.x + head_blocks, B), 256, 0, st>>>(grad_prob, N, counts, P, ws, L, grad_scores, (int)ge.x);
             GNMS_CHECK_LAUNCH();
         } else {
