@@ -42,7 +42,8 @@ __device__ __forceinline__ float rank_term(float v, float x, float two_delta) {
 // kApE elements per thread: the workgroup ranks up to P = 1024 * kApE boxes (LDS arrays and the sort are sized by P).
 template <int kApE>
 __global__ __launch_bounds__(kApThreads) void aploss_kernel(const float* __restrict__ logits, const float* __restrict__ targets, int N,
-                                                      const int* __restrict__ counts, float positive_label, float negative_label,
+                                                      const int* __restrict__ counts, const int* __restrict__ tail_counts,
+                                                      float positive_label, float negative_label,
                                                       float* __restrict__ loss, float* __restrict__ grad) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int P = kApThreads * kApE;
@@ -89,6 +90,10 @@ __global__ __launch_bounds__(kApThreads) void aploss_kernel(const float* __restr
         return;
     }
     const float threshold_logit = fmin - 1.0f;                        // :32
+    // the implicit tail (gnms_aploss_tail): tail_counts[b] further negatives of logit 0 behind the n explicit boxes.  They are valid
+    // negatives when 0 >= min positive - 1 (:35) and then add tail * clamp((0 - x_p) / 2 + 0.5, 0, 1) to every b_p; they have no
+    // gradient output.  Without a tail nothing below changes by a bit.
+    const int tail = (tail_counts && tail_counts[b] > 0 && 0.0f >= threshold_logit) ? tail_counts[b] : 0;
 
     // ---- pass 2: classify, compact (positives -> keys, valid negatives -> bgv) ----
     int cls[kApE];                                                    // 1 positive, 2 valid negative, 0 neither
@@ -145,6 +150,7 @@ __global__ __launch_bounds__(kApThreads) void aploss_kernel(const float* __restr
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) { sa += __shfl_xor(sa, off, 64); sb += __shfl_xor(sb, off, 64); }
         if (lane == 0) {
+            if (tail > 0) sb += (double)tail * (double)rank_term(0.0f, x, two_delta);
             const float a = (float)sa + 0.5f;                         // :58
             const float bsum = (float)sb;                             // :60
             denom[p] = a + bsum;
@@ -518,21 +524,22 @@ __global__ __launch_bounds__(256) void ap_neg_grad_kernel(int N, float* __restri
 
 }  // namespace
 
-extern "C" int gnms_aploss(const float* logits, const float* targets, int B, int N, const int32_t* counts, float positive_label,
-                           float negative_label, float* loss, float* grad, void* stream) {
-    GNMS_CHECK_ARG(B >= 0 && N >= 0, "gnms_aploss: negative size");
+// tail_counts == nullptr: gnms_aploss as it always was; otherwise gnms_aploss_tail (N <= kApMaxN, the LDS kernel whatever B is)
+static int aploss_impl(const float* logits, const float* targets, int B, int N, const int32_t* counts, const int32_t* tail_counts,
+                       float positive_label, float negative_label, float* loss, float* grad, void* stream, const char* who) {
+    GNMS_CHECK_ARG(B >= 0 && N >= 0, "%s: negative size", who);
     if (B == 0) return GNMS_OK;
-    GNMS_CHECK_ARG(loss != nullptr, "gnms_aploss: loss is NULL");
+    GNMS_CHECK_ARG(loss != nullptr, "%s: loss is NULL", who);
     hipStream_t st = (hipStream_t)stream;
     if (N == 0) { GNMS_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(float) * B, st)); return GNMS_OK; }
     if (N > GNMS_MAX_BOXES) {
         gnms_set_error("gnms_aploss: N=%d exceeds GNMS_MAX_BOXES=%d", N, GNMS_MAX_BOXES);
         return GNMS_ERR_UNSUPPORTED;
     }
-    GNMS_CHECK_ARG(logits && targets && grad, "gnms_aploss: null pointer");
+    GNMS_CHECK_ARG(logits && targets && grad, "%s: null pointer", who);
     // One workgroup per image ranks up to 4096 boxes entirely in LDS; larger images -- and smaller batches of images from 2048 boxes,
     // whose F x N product makes the one-CU version slow -- run the four-kernel version that spreads the positives over the machine.
-    if (N > kApMaxN || (N >= 2048 && B <= 64)) {
+    if (!tail_counts && (N > kApMaxN || (N >= 2048 && B <= 64))) {
         gnms_async_buffer scratch_buf;                                // returned to the pool on every exit, the early error returns included
         GNMS_CHECK_HIP(scratch_buf.alloc((size_t)B * ap_scratch_words(N) * sizeof(float), st));
         float* scratch = scratch_buf.as<float>();
@@ -565,11 +572,27 @@ extern "C" int gnms_aploss(const float* logits, const float* targets, int B, int
         GNMS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(aploss_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            kApThreads * 4 * 4 * 6));
 #define GNMS_APLOSS_LAUNCH(E) \
-    aploss_kernel<E><<<B, kApThreads, (size_t)kApThreads * E * 4 * 6, st>>>(logits, targets, N, counts, positive_label, negative_label, loss, grad)
+    aploss_kernel<E><<<B, kApThreads, (size_t)kApThreads * E * 4 * 6, st>>>(logits, targets, N, counts, tail_counts, positive_label, negative_label, loss, grad)
     if (N <= kApThreads) GNMS_APLOSS_LAUNCH(1);
     else if (N <= 2 * kApThreads) GNMS_APLOSS_LAUNCH(2);
     else GNMS_APLOSS_LAUNCH(4);
 #undef GNMS_APLOSS_LAUNCH
     GNMS_CHECK_LAUNCH();
     return GNMS_OK;
+}
+
+extern "C" int gnms_aploss(const float* logits, const float* targets, int B, int N, const int32_t* counts, float positive_label,
+                           float negative_label, float* loss, float* grad, void* stream) {
+    return aploss_impl(logits, targets, B, N, counts, nullptr, positive_label, negative_label, loss, grad, stream, "gnms_aploss");
+}
+
+// gnms_aploss with an implicit tail of zero-logit negatives per image: always the one-workgroup LDS kernel, so N <= 4096
+extern "C" int gnms_aploss_tail(const float* logits, const float* targets, int B, int N, const int32_t* counts, const int32_t* tail_counts,
+                                float positive_label, float negative_label, float* loss, float* grad, void* stream) {
+    GNMS_CHECK_ARG(tail_counts != nullptr, "gnms_aploss_tail: tail_counts is NULL");
+    if (N > kApMaxN) {
+        gnms_set_error("gnms_aploss_tail: N=%d exceeds %d (one workgroup ranks the explicit boxes in LDS)", N, kApMaxN);
+        return GNMS_ERR_UNSUPPORTED;
+    }
+    return aploss_impl(logits, targets, B, N, counts, tail_counts, positive_label, negative_label, loss, grad, stream, "gnms_aploss_tail");
 }

@@ -1365,6 +1365,20 @@ OneLaunchPlan one_launch_plan(int src, int B, int N, const gnms_params& P) {
     }
     return p;
 }
+// The one launch zeroes nothing of the workspace: its roles hand over through granules that carry tag = next(misc[8]).  A recycled workspace
+// can hold an EARLIER call's granules beside a counter that something else has overwritten since (another tensor of the caching allocator,
+// an allocation of the same captured graph) -- then the new tag can equal the stale granules' and a role goes ahead on the previous call's
+// data (seen: csr_build_body built the backward's runs from the last call's heads; the probabilities were right, dL/dscores was not).
+// So the granules of every image are cleared in front of the launch, stream-ordered: a cleared granule carries tag 0, which no call uses.
+__global__ __launch_bounds__(256) void clear_granules_kernel(char* ws, gnms_ws_layout L) {
+    u64* g = reinterpret_cast<u64*>(ws + (size_t)blockIdx.x * L.per_image + L.off_gran);
+    for (int i = threadIdx.x; i < 17 * 32; i += 256) g[i] = 0ull;
+}
+int clear_granules(const LayerCall& c) {
+    clear_granules_kernel<<<c.B, 256, 0, c.st>>>(c.ws, c.L);
+    GNMS_CHECK_LAUNCH();
+    return GNMS_OK;
+}
 // (both launchers: *launched stays false where the call does not take the one launch)
 int launch_one_matrix(const LayerCall& c, const float* scores, const float* iou, int64_t ld, bool* launched) {
     *launched = false;
@@ -1374,6 +1388,7 @@ int launch_one_matrix(const LayerCall& c, const float* scores, const float* iou,
     const size_t lds = one_launch_lds_size(c.N, false);
     int rc;
     if ((rc = allow_lds(one_launch_kernel<kFromMatrix>, lds))) return rc;
+    if ((rc = clear_granules(c))) return rc;
     // (profile slot of the matrix READ: this launch holds the layer's one pass over the matrix -- bench.py's `roofline_matrix_in`)
     gnms_launch_prof(kProfMatrixRead, one_launch_kernel<kFromMatrix>, dim3((unsigned)plan.front), dim3(1024), lds, c.st, scores, iou, c.N, (long)ld, c.counts, c.P, c.ws, c.L,
                      c.prob, (long long*)c.valid, (long long*)c.invalid, c.nvalid, c.ninvalid, (long long*)c.order, c.B, plan.kpw, plan.split);
@@ -1404,6 +1419,7 @@ int launch_one_boxes(const LayerCall& c, const float* scores, const float* boxes
     size_t lds = one_launch_lds_size(N, true);
     if (lds < (size_t)N * 16) lds = (size_t)N * 16;
     if ((rc = allow_lds(one_launch_boxes_kernel, lds))) return rc;
+    if ((rc = clear_granules(c))) return rc;
     gnms_launch_prof(kProfMatrixWrite, one_launch_boxes_kernel, dim3((unsigned)(plan.front + writers)), dim3(1024), lds, c.st, scores, boxes, N, c.counts, c.P, c.ws, c.L,
                      c.prob, (long long*)c.valid, (long long*)c.invalid, c.nvalid, c.ninvalid, (long long*)c.order, B, plan.kpw, plan.tpw, out, (long)ld, claims,
                      (int)writers);

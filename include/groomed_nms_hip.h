@@ -654,6 +654,55 @@ int gnms_reg_loss(const float* bbox_2d, const float* bbox_3d, int ld_bbox_3d, co
                   int32_t* stat_counts, float* d_bbox_2d, float* d_bbox_3d, float* d_acceptance, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The after-NMS block of the loss (lib/loss/rpn_3d.py:721-825, :1091-1148) from the heads (csrc/after_nms.hip), around
+ * gnms_select_topk, the layer and gnms_best_targets.  Stream-ordered launches only, no allocation, nothing read back.
+ * ------------------------------------------------------------------------------------------------ */
+/* gnms_aploss with an implicit tail: image b is ranked as if tail_counts[b] further negatives of logit 0 followed its explicit boxes
+ * (the sampled foreground beyond the boxes that went through the NMS, :1124-1128, whose scores_after_nms and targets_after_nms are 0).
+ * Where 0 >= min positive - 1 (aploss.py:32-35) every positive's b_p gets tail * clamp((0 - x_p) / 2 + 0.5, 0, 1); the tail has no
+ * gradient output.  One workgroup per image in LDS whatever B is: N <= 4096, GNMS_ERR_UNSUPPORTED above.  tail_counts all 0: the bits
+ * of gnms_aploss's LDS route. */
+int gnms_aploss_tail(const float* logits, const float* targets, int B, int N, const int32_t* counts, const int32_t* tail_counts,
+                     float positive_label, float negative_label, float* loss, float* grad, void* stream);
+/* Gather and decode of the selected anchors, one launch.  sel_index [B][K] / sel_counts [B] from gnms_select_topk.  Heads bbox_2d
+ * [B][R][4] (16-byte aligned), bbox_3d [B][R][D3 >= 10]; raw_gt (>= 21 columns: [19] axis label, [20] head label), rois (>= 4), rois_3d
+ * (>= 11) read where they lie, anchor r of image b at (b * R + r) * ld; rois_3d_cen [B][R][2]; p2 [B][p2_rows][4] and scale_factor [B]
+ * float64 on the device; means / stds 13 values each ON THE HOST.  gts_val [B][M][4], gts_3d [B][M][ld_gts_3d >= 11] float64 and
+ * val_counts [B] as gnms_compute_targets takes them.
+ * boxes2d [B][K][4] = bbox_transform_inv(rois[b], bbox_2d, means[:4], stds[:4]) of the selected rows (the device code of
+ * gnms_bbox_transform_inv; not divided by the scale).  cuboids [B][K][7] = x y z w h l ry in camera space, fp32 in the reference's
+ * operation order (:318-363, :532-574): the rotation is rois_3d[9] + rsin where raw_gt[19] == 1, else rois_3d[10] + rcos, + pi where
+ * raw_gt[20] == 1, snapped into (-pi, pi] (bounded loop; a non-finite angle stays), then alpha -> rotation_y (util.py:635-638).
+ * gt_params [B][M][7] = gts_3d columns 7 8 9 3 4 5 10, gt_boxes [B][M][4] (:801-811).  Rows behind an image's count are zero. */
+int gnms_after_nms_decode(const int64_t* sel_index, const int32_t* sel_counts, int B, int K, int R, const float* bbox_2d,
+                          const float* bbox_3d, int D3, const float* raw_gt, int64_t ld_raw_gt, const float* rois, int ld_rois,
+                          const float* rois_3d, int ld_rois_3d, const float* rois_3d_cen, const double* p2, int p2_rows,
+                          const double* scale_factor, const double* means_host, const double* stds_host, const double* gts_val,
+                          const double* gts_3d, int ld_gts_3d, int M, const int32_t* val_counts, float* boxes2d, float* cuboids,
+                          float* gt_params, float* gt_boxes, void* stream);
+/* One workgroup.  mode 0: rank per image, 1: rank all images at once, 2: classify.  fg_counts [B] = sampled foreground per image.
+ * phase 0 (in front of gnms_aploss_tail): tail_counts [B + 1] = max(fg_counts - sel_counts, 0) per image, then their sum;
+ *   targets [B][K] (written) = 1 where some best_index[b][m] (gnms_best_targets, [B][M]) names the box, else 0;
+ *   targets_padded [B][K] = targets, -1 behind sel_counts (mode 1 ranks it as ONE row of B * K with the summed tail).
+ * phase 1: img_cnt [1] = #{b: fg_counts[b] > 0}; loss [2 + B] = the loss, the statistic (the same value), the per-image AP losses
+ *   (0 in modes 1, 2); dprob [B][K] = d loss / d (rescored probability), 0 behind sel_counts.
+ *   mode 0: loss = lambda * sum over counted images of ap_loss[b] / img_cnt, dprob = ap_grad * lambda / img_cnt (:1121-1131);
+ *   mode 1: loss = lambda * ap_loss[0] (:1119); no sampled foreground in the batch: loss 0, dprob 0 (:1100-1101).
+ *   mode 2 (:1103-1115): binary cross entropy of prob against targets, logs clamped at -100, negatives weighted by
+ *   (n_pos / n_neg)^0.25 when both are positive, mean over the finite elements; the zero tail counts in n_neg and in the mean; an
+ *   element the filter drops gets gradient 0. */
+int gnms_after_nms_finish(int phase, int mode, int B, int K, const int32_t* fg_counts, const int32_t* sel_counts, const float* prob,
+                          float* targets, const float* ap_loss, const float* ap_grad, float after_nms_lambda,
+                          int32_t* tail_counts, float* targets_padded, float* loss, int32_t* img_cnt, float* dprob,
+                          const int64_t* best_index, int M, void* stream);
+/* The backward scatter: dscore [B][K] = d loss / d (score that went into the layer) -> the heads' dense gradients, every element
+ * written, 0 off the selection.  acceptance [B][R] with dacceptance, prob [B][R][C] with cls_pred [B][R] (gnms_detect3d_scores) and
+ * dprob where the scores read max(prob[1:]): dacceptance = dscore (* that maximum), dprob[cls_pred] = dscore (* acceptance). */
+int gnms_after_nms_scatter(const int64_t* sel_index, const int32_t* sel_counts, const float* dscore, int B, int K, int R, int C,
+                           const float* acceptance, const float* prob, const int32_t* cls_pred, float* dacceptance, float* dprob,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
