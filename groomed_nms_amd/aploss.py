@@ -3,8 +3,10 @@
 `APLoss` / `backpropAPLoss` keep the reference's names, arguments, defaults and return shapes
 (lib/loss/aploss.py:12-97; used at lib/loss/rpn_3d.py:189 and :1117-1131 on the scores GrooMeD-NMS
 rescored).  The ranking itself -- the reference's Python loop over the positives, O(N) tensor ops per
-trip (:50-68) -- runs behind `gnms_aploss` (include/groomed_nms_hip.h): one workgroup per image up to 2047 boxes,
-four launches that spread the positives over the machine above that (up to 16384 boxes per image).
+trip (:50-68) -- runs behind `gnms_aploss` (include/groomed_nms_hip.h): one workgroup per image that ranks everything in LDS
+for N < 2048 boxes, and for N <= 4096 when the batch has more than 64 images (or the call carries a tail of implicit negatives,
+`gnms_aploss_tail`, groomed_nms_amd/after_nms.py); four launches that spread the positives over the machine otherwise
+(2048 <= N <= 4096 with B <= 64, and every N above 4096 up to 16384 boxes per image).
 No CPU implementation lives here: without the library or a GPU the calls raise.
 """
 import torch

@@ -4,7 +4,14 @@
 // (lib/loss/rpn_3d.py:1117-1131).  The reference walks the positives in ascending-logit order in a PYTHON loop, every
 // trip doing O(N) tensor ops (:50-68); loss and gradient both come out of forward (:69-78), backward only scales (:80-85).
 //
-// Here: one workgroup per image, everything in LDS.
+// Two versions of one computation, chosen by aploss_impl at the end of this file:
+//   aploss_kernel<E>   one workgroup per image, everything in LDS (E = 1, 2, 4 elements per thread for N <= 1024, 2048, 4096):
+//                      N < 2048; N <= 4096 when B > 64 or when the call carries a tail (gnms_aploss_tail, which has no other route)
+//   the spread kernels four launches that deal the positives over the machine (second half of this file): everything else, that is
+//                      2048 <= N <= 4096 with B <= 64 and no tail, and 4096 < N <= GNMS_MAX_BOXES
+// Both are held to a float64 restatement of the reference on every route: tests/test_aploss_host.py, tests/test_aploss_gpu.py.
+//
+// aploss_kernel:
 //   1. classify + compact (packed block scan): positives -> sortable keys, "valid" negatives (logit >= min positive - delta, :32-35)
 //   2. sort the positive VALUES (block_sort, u32 keys; ties need no index: equal logits get equal precision and add equal terms)
 //   3. per positive p (one thread each): a_p = sum_k clamp((fg_k - x_p)/(2 delta) + 0.5, 0, 1) + 0.5,  b_p likewise over the valid
