@@ -703,6 +703,35 @@ int gnms_after_nms_scatter(const int64_t* sel_index, const int32_t* sel_counts, 
                            const float* acceptance, const float* prob, const int32_t* cls_pred, float* dacceptance, float* dprob,
                            void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The RPN heads' maps -> the five tensors every entry behind the network reads (csrc/heads.hip): what
+ * models/densenet121_3d_dilate_decomp_alpha.py:166-215 builds from its fifteen 1x1 convolutions.  One launch each, no workspace, no
+ * atomics, nothing filled beforehand, nothing read back; the host arrays are read before the call returns and travel in the kernel's
+ * arguments, so both entries can be captured into a graph.
+ * R = A * H * W, anchor row r = (a * H + h) * W + w (locate_anchors(..., convert_tensor=True); view(B, C, A * H, W) + flatten_tensor).
+ * maps [15], float32 on the device: the class logits [B][C * A][H][W] (channel c * A + a), the thirteen box maps [B][A][H][W] in the
+ * order x y w h x3d y3d z3d w3d h3d l3d alpha axis head (axis and head before their sigmoid), the acceptance map [B][A][H][W] or NULL.
+ * Image b of map k starts batch_strides[k] elements behind image b - 1 (>= 0; a channel slice of a stacked output keeps the stacked
+ * stride); its [., H, W] block is contiguous.
+ *   cls [B][R][C]      = cls_map[b].flat[c * R + r]
+ *   prob [B][R][C]     = softmax over c: exp(x - max) / sum, expf and a true division
+ *   bbox_2d [B][R][4]  = x y w h
+ *   bbox_3d [B][R][10] = x3d y3d z3d w3d h3d l3d alpha alpha sigmoid(axis) sigmoid(head), sigmoid(x) = 1 / (1 + expf(-x))
+ *   acceptance [B][R]  = sigmoid(acceptance map); not touched without the map
+ * cls, prob, bbox_2d, bbox_3d 16-byte aligned.  2 <= C <= 16 (GNMS_ERR_UNSUPPORTED outside).  B = 0: GNMS_OK, nothing is done. */
+int gnms_heads_assemble(const void* const* maps, const long long* batch_strides, int B, int A, int H, int W, int C, float* cls,
+                        float* prob, float* bbox_2d, float* bbox_3d, float* acceptance, void* stream);
+/* The backward: prob, bbox_3d, acceptance as gnms_heads_assemble wrote them, the five cotangents (contiguous rows; one that is NULL is
+ * zero and then needs no forward tensor either), and grad_maps [15]: contiguous float32 [B][.][H][W] like the maps, every element
+ * written; an entry that is NULL is not computed.
+ *   d cls_map[c] = g_cls[c] + prob[c] * (g_prob[c] - sum_j g_prob[j] * prob[j])
+ *   d alpha = g_bbox_3d[6] + g_bbox_3d[7];  d axis = g_bbox_3d[8] * s * (1 - s) with s = bbox_3d[8], head ([9]) and acceptance alike;
+ *   the other ten maps get their cotangent column.
+ * prob and the cotangents of cls, prob, bbox_2d, bbox_3d 16-byte aligned, bbox_3d 8-byte. */
+int gnms_heads_assemble_backward(const float* prob, const float* bbox_3d, const float* acceptance, const float* g_cls,
+                                 const float* g_prob, const float* g_bbox_2d, const float* g_bbox_3d, const float* g_acceptance, int B,
+                                 int A, int H, int W, int C, void* const* grad_maps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
