@@ -150,6 +150,11 @@ _SIGNATURES = {
                                            c_vp, c_vp, c_vp]),
     "gnms_heads_assemble_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                     ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "gnms_gt_filter": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gnms_loss_combine": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gnms_loss_grad_combine": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                              c_vp, c_vp, c_vp, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -51,23 +51,14 @@ class _AfterNMSLoss(torch.autograd.Function):
         return (None,) + tuple(grads)
 
 
-def after_nms_loss(prob, acceptance, bbox_2d, bbox_3d, targets, sample, rois, rois_3d, rois_3d_cen, p2, scale_factor, gts_val, gts_3d,
-                   val_counts, *, means, stds, after_nms_lambda=0.05, after_nms_loss_mode="rank", rank_boxes_of_all_images_at_once=False,
-                   rank_with_class_confidence=False, best_target_box_beta=0.3, nms_threshold=0.4, pruning_method="linear", temperature=0.1,
-                   valid_box_prob_threshold=0.3, group_boxes=True, mask_group_boxes=True, group_size=100, diff_nms_boxes_2d="normal",
-                   overlap_in_nms="2d", max_nms_boxes=500, decomp_alpha=True):
-    """prob [B, R, C] (column 0 = background), acceptance [B, R] or None, bbox_2d [B, R, 4], bbox_3d [B, R, >= 10]: the heads.  targets:
-    Targets of compute_targets_batched or a (transforms, raw_gt) pair (raw_gt [B, R, >= 21] is read where it lies, with a row stride);
-    sample: Sample of sample_anchors; rois [B, R, >= 4], rois_3d [B, R, >= 11], rois_3d_cen [B, R, 2]; p2 [B, 3 or 4, 4] and
-    scale_factor [B] (float64 on the device); gts_val [B, M, 4], gts_3d [B, M, >= 11], val_counts [B] as compute_targets_batched takes
-    them (the cuboid of a ground truth is columns 7, 8, 9, 3, 4, 5, 10).  means / stds: 13 host values each.
-    The score of an anchor is acceptance (times max(prob[1:]) with rank_with_class_confidence, one fp32 product), or max(prob[1:])
-    without an acceptance head.  Images with sample.counts[b, 2] > 0 (the quota) send the min(max_nms_boxes, fg_counts[b]) best of
-    sample.fg_index[b, :fg_counts[b]] through the NMS.
-    -> (loss, info): loss a scalar tensor, differentiable w.r.t. acceptance (and prob where the scores read it); info a dict of device
-    tensors: the statistic under the reference's name (bbox_after_nms_rank / bbox_after_nms_class), sel_index [B, K] int64 (-1 behind
-    sel_counts [B]), scores_after_nms / targets_after_nms [B, K] in selection order, losses [B] (the per-image AP losses; 0 in the other
-    modes) and img_cnt (int32 scalar).  Without sampled foreground in the batch: loss 0, gradients 0."""
+def _after_nms_term(prob, acceptance, bbox_2d, bbox_3d, targets, sample, rois, rois_3d, rois_3d_cen, p2, scale_factor, gts_val, gts_3d,
+                    val_counts, *, means, stds, after_nms_lambda=0.05, after_nms_loss_mode="rank", rank_boxes_of_all_images_at_once=False,
+                    rank_with_class_confidence=False, best_target_box_beta=0.3, nms_threshold=0.4, pruning_method="linear", temperature=0.1,
+                    valid_box_prob_threshold=0.3, group_boxes=True, mask_group_boxes=True, group_size=100, diff_nms_boxes_2d="normal",
+                    overlap_in_nms="2d", max_nms_boxes=500, decomp_alpha=True):
+    """after_nms_loss up to the launches -> (run, info, use_prob): run() launches the chain on the detached heads and returns (loss [],
+    dacc [B, R] or None, dprob [B, R, C] or None), loss being element 0 of gnms_after_nms_finish's loss array; info is filled by it;
+    use_prob: the scores read prob.  (Shared with loss.RPN_3D_loss, which scales the gradients in its one backward launch.)"""
     if after_nms_loss_mode not in ("rank", "classify"):
         raise NotImplementedError("after_nms_loss implements after_nms_loss_mode 'rank' and 'classify', not %r" % (after_nms_loss_mode,))
     if overlap_in_nms != "2d":
@@ -228,5 +219,34 @@ def after_nms_loss(prob, acceptance, bbox_2d, bbox_3d, targets, sample, rois, ro
         info["img_cnt"] = img_cnt.reshape(())
         return out_loss[0], dacc, dprob
 
+    return run, info, use_prob
+
+
+def after_nms_loss(prob, acceptance, bbox_2d, bbox_3d, targets, sample, rois, rois_3d, rois_3d_cen, p2, scale_factor, gts_val, gts_3d,
+                   val_counts, *, means, stds, after_nms_lambda=0.05, after_nms_loss_mode="rank", rank_boxes_of_all_images_at_once=False,
+                   rank_with_class_confidence=False, best_target_box_beta=0.3, nms_threshold=0.4, pruning_method="linear", temperature=0.1,
+                   valid_box_prob_threshold=0.3, group_boxes=True, mask_group_boxes=True, group_size=100, diff_nms_boxes_2d="normal",
+                   overlap_in_nms="2d", max_nms_boxes=500, decomp_alpha=True):
+    """prob [B, R, C] (column 0 = background), acceptance [B, R] or None, bbox_2d [B, R, 4], bbox_3d [B, R, >= 10]: the heads.  targets:
+    Targets of compute_targets_batched or a (transforms, raw_gt) pair (raw_gt [B, R, >= 21] is read where it lies, with a row stride);
+    sample: Sample of sample_anchors; rois [B, R, >= 4], rois_3d [B, R, >= 11], rois_3d_cen [B, R, 2]; p2 [B, 3 or 4, 4] and
+    scale_factor [B] (float64 on the device); gts_val [B, M, 4], gts_3d [B, M, >= 11], val_counts [B] as compute_targets_batched takes
+    them (the cuboid of a ground truth is columns 7, 8, 9, 3, 4, 5, 10).  means / stds: 13 host values each.
+    The score of an anchor is acceptance (times max(prob[1:]) with rank_with_class_confidence, one fp32 product), or max(prob[1:])
+    without an acceptance head.  Images with sample.counts[b, 2] > 0 (the quota) send the min(max_nms_boxes, fg_counts[b]) best of
+    sample.fg_index[b, :fg_counts[b]] through the NMS.
+    -> (loss, info): loss a scalar tensor, differentiable w.r.t. acceptance (and prob where the scores read it); info a dict of device
+    tensors: the statistic under the reference's name (bbox_after_nms_rank / bbox_after_nms_class), sel_index [B, K] int64 (-1 behind
+    sel_counts [B]), scores_after_nms / targets_after_nms [B, K] in selection order, losses [B] (the per-image AP losses; 0 in the other
+    modes) and img_cnt (int32 scalar).  Without sampled foreground in the batch: loss 0, gradients 0."""
+    run, info, use_prob = _after_nms_term(prob, acceptance, bbox_2d, bbox_3d, targets, sample, rois, rois_3d, rois_3d_cen, p2, scale_factor, gts_val,
+                                          gts_3d, val_counts, means=means, stds=stds, after_nms_lambda=after_nms_lambda,
+                                          after_nms_loss_mode=after_nms_loss_mode,
+                                          rank_boxes_of_all_images_at_once=rank_boxes_of_all_images_at_once,
+                                          rank_with_class_confidence=rank_with_class_confidence, best_target_box_beta=best_target_box_beta,
+                                          nms_threshold=nms_threshold, pruning_method=pruning_method, temperature=temperature,
+                                          valid_box_prob_threshold=valid_box_prob_threshold, group_boxes=group_boxes,
+                                          mask_group_boxes=mask_group_boxes, group_size=group_size, diff_nms_boxes_2d=diff_nms_boxes_2d,
+                                          overlap_in_nms=overlap_in_nms, max_nms_boxes=max_nms_boxes, decomp_alpha=decomp_alpha)
     loss = _AfterNMSLoss.apply(run, acceptance, prob if use_prob else None)
     return loss, info

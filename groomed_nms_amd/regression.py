@@ -65,21 +65,14 @@ def _rows(t, dev, B, R, min_cols, what):
     return t, t.stride(1)
 
 
-def regression_loss(bbox_2d, bbox_3d, acceptance, targets, sample, rois, rois_3d, rois_3d_cen, p2, scale_factor, *, means, stds,
-                    bbox_2d_lambda=0.0, bbox_3d_lambda=1.0, bbox_axis_head_lambda=0.35, iou_2d_lambda=1.0,
-                    use_acceptance_prob_in_regression_loss=False, bbox_un_lambda=0.0, bbox_un_dynamic=False, un_state=None,
-                    decomp_alpha=True, orientation_bins=0, infer_2d_from_3d=False, has_un=False,
-                    weigh_3D_regression_loss_by_gt_iou3d=False):
-    """bbox_2d [B, R, 4], bbox_3d [B, R, >= 10] (x, y, z, w, h, l, rsin, rcos, axis, head; further columns get gradient 0), acceptance
-    [B, R] or None: the heads, differentiable.  targets: Targets of compute_targets_batched (normalised transforms [B, R, >= 14], raw_gt
-    [B, R, >= 21]; views with a row stride are read where they lie) or a (transforms, raw_gt) pair; sample: Sample of sample_anchors;
-    rois [B, R, >= 4], rois_3d [B, R, >= 11], rois_3d_cen [B, R, 2]; p2 [B, 3 or 4, 4] and scale_factor [B] (float64 on the device).
-    means / stds: 13 host values each (conf.bbox_means[0], conf.bbox_stds[0]).  With bbox_un_dynamic, un_state is the caller-owned
-    device state of new_un_state(); it is advanced by the call, on the device.
-    -> (loss, stats): loss a scalar tensor, differentiable w.r.t. the three heads; stats a dict of device scalars (float64) named as the
-    reference's (STAT_NAMES), `total` being the sum of these terms and `bbox_un_lambda` the uncertainty weight in use, plus `counts`
-    (int32 [24], GNMS_REG_STAT_COUNTS).  Without an active anchor in the batch: loss 0, gradients 0, statistics NaN, un_state untouched.
-    See the module's docstring for the two deliberate differences from the reference and for rois[b]."""
+def _reg_term(bbox_2d, bbox_3d, acceptance, targets, sample, rois, rois_3d, rois_3d_cen, p2, scale_factor, *, means, stds,
+              bbox_2d_lambda=0.0, bbox_3d_lambda=1.0, bbox_axis_head_lambda=0.35, iou_2d_lambda=1.0,
+              use_acceptance_prob_in_regression_loss=False, bbox_un_lambda=0.0, bbox_un_dynamic=False, un_state=None,
+              decomp_alpha=True, orientation_bins=0, infer_2d_from_3d=False, has_un=False,
+              weigh_3D_regression_loss_by_gt_iou3d=False):
+    """regression_loss up to the launch -> (run, stats, stat_counts): run() launches gnms_reg_loss on the detached heads and returns
+    (loss [], d2 [B, R, 4], d3 [B, R, D3], da [B, R] or None); stats [14] float64 and stat_counts [24] int32 are filled by it.  (Shared with
+    loss.RPN_3D_loss, which scales the gradients in its one backward launch.)"""
     if not decomp_alpha or orientation_bins or infer_2d_from_3d or has_un or weigh_3D_regression_loss_by_gt_iou3d:
         raise NotImplementedError("regression_loss implements decomp_alpha=True, orientation_bins=0, infer_2d_from_3d=False, has_un=False, "
                                   "weigh_3D_regression_loss_by_gt_iou3d=False")
@@ -151,6 +144,31 @@ def regression_loss(bbox_2d, bbox_3d, acceptance, targets, sample, rois, rois_3d
         check(rc, "gnms_reg_loss")
         return loss.reshape(()), d2, d3, da
 
+    return run, stats, stat_counts
+
+
+def regression_loss(bbox_2d, bbox_3d, acceptance, targets, sample, rois, rois_3d, rois_3d_cen, p2, scale_factor, *, means, stds,
+                    bbox_2d_lambda=0.0, bbox_3d_lambda=1.0, bbox_axis_head_lambda=0.35, iou_2d_lambda=1.0,
+                    use_acceptance_prob_in_regression_loss=False, bbox_un_lambda=0.0, bbox_un_dynamic=False, un_state=None,
+                    decomp_alpha=True, orientation_bins=0, infer_2d_from_3d=False, has_un=False,
+                    weigh_3D_regression_loss_by_gt_iou3d=False):
+    """bbox_2d [B, R, 4], bbox_3d [B, R, >= 10] (x, y, z, w, h, l, rsin, rcos, axis, head; further columns get gradient 0), acceptance
+    [B, R] or None: the heads, differentiable.  targets: Targets of compute_targets_batched (normalised transforms [B, R, >= 14], raw_gt
+    [B, R, >= 21]; views with a row stride are read where they lie) or a (transforms, raw_gt) pair; sample: Sample of sample_anchors;
+    rois [B, R, >= 4], rois_3d [B, R, >= 11], rois_3d_cen [B, R, 2]; p2 [B, 3 or 4, 4] and scale_factor [B] (float64 on the device).
+    means / stds: 13 host values each (conf.bbox_means[0], conf.bbox_stds[0]).  With bbox_un_dynamic, un_state is the caller-owned
+    device state of new_un_state(); it is advanced by the call, on the device.
+    -> (loss, stats): loss a scalar tensor, differentiable w.r.t. the three heads; stats a dict of device scalars (float64) named as the
+    reference's (STAT_NAMES), `total` being the sum of these terms and `bbox_un_lambda` the uncertainty weight in use, plus `counts`
+    (int32 [24], GNMS_REG_STAT_COUNTS).  Without an active anchor in the batch: loss 0, gradients 0, statistics NaN, un_state untouched.
+    See the module's docstring for the two deliberate differences from the reference and for rois[b]."""
+    run, stats, stat_counts = _reg_term(bbox_2d, bbox_3d, acceptance, targets, sample, rois, rois_3d, rois_3d_cen, p2, scale_factor, means=means,
+                                        stds=stds, bbox_2d_lambda=bbox_2d_lambda, bbox_3d_lambda=bbox_3d_lambda,
+                                        bbox_axis_head_lambda=bbox_axis_head_lambda, iou_2d_lambda=iou_2d_lambda,
+                                        use_acceptance_prob_in_regression_loss=use_acceptance_prob_in_regression_loss,
+                                        bbox_un_lambda=bbox_un_lambda, bbox_un_dynamic=bbox_un_dynamic, un_state=un_state,
+                                        decomp_alpha=decomp_alpha, orientation_bins=orientation_bins, infer_2d_from_3d=infer_2d_from_3d,
+                                        has_un=has_un, weigh_3D_regression_loss_by_gt_iou3d=weigh_3D_regression_loss_by_gt_iou3d)
     loss = _RegLoss.apply(run, bbox_2d, bbox_3d, acceptance)
     out = {name: stats[i] for i, name in enumerate(STAT_NAMES)}
     out["counts"] = stat_counts

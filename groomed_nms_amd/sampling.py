@@ -101,10 +101,10 @@ class _ClsLoss(torch.autograd.Function):
         return (dcls * grad_output).to(dtype).reshape(shape), None
 
 
-def classification_loss(cls, sample, *, fg_fraction, focal_loss=0, cls_2d_lambda=1):
-    """cls [B, R, C] logits, sample from sample_anchors -> (loss, stats): loss a scalar tensor (differentiable w.r.t. cls), stats a
-    dict of device scalars: acc_fg / acc_bg (float64; NaN when the batch has no such label) and cls (the term, detached).
-    Fills sample.labels_weight."""
+def _cls_term(cls, sample, *, fg_fraction, focal_loss=0, cls_2d_lambda=1):
+    """classification_loss up to the launch -> (run, acc): run(x) launches gnms_cls_loss on the detached logits x and returns (loss [],
+    dcls [B, R, C]); acc [2] float64 is filled by it.  Fills sample.labels_weight.  (Shared with loss.RPN_3D_loss, which scales dcls in
+    its one backward launch.)"""
     lib = _lib.load()
     if sample.sampled is None:
         raise ValueError("sample must come from sample_anchors")
@@ -131,6 +131,14 @@ def classification_loss(cls, sample, *, fg_fraction, focal_loss=0, cls_2d_lambda
         check(rc, "gnms_cls_loss")
         return loss.reshape(()), dcls
 
-    loss = _ClsLoss.apply(cls, run)
     sample.labels_weight = labels_weight
+    return run, acc
+
+
+def classification_loss(cls, sample, *, fg_fraction, focal_loss=0, cls_2d_lambda=1):
+    """cls [B, R, C] logits, sample from sample_anchors -> (loss, stats): loss a scalar tensor (differentiable w.r.t. cls), stats a
+    dict of device scalars: acc_fg / acc_bg (float64; NaN when the batch has no such label) and cls (the term, detached).
+    Fills sample.labels_weight."""
+    run, acc = _cls_term(cls, sample, fg_fraction=fg_fraction, focal_loss=focal_loss, cls_2d_lambda=cls_2d_lambda)
+    loss = _ClsLoss.apply(cls, run)
     return loss, {"acc_fg": acc[0], "acc_bg": acc[1], "cls": loss.detach()}

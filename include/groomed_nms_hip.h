@@ -732,6 +732,46 @@ int gnms_heads_assemble_backward(const float* prob, const float* bbox_3d, const 
                                  const float* g_prob, const float* g_bbox_2d, const float* g_bbox_3d, const float* g_acceptance, int B,
                                  int A, int H, int W, int C, void* const* grad_maps, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * RPN_3D_loss around its terms (csrc/loss.hip): the ground truths of a batch from packed records, the total with the
+ * reference's statistics, and the whole backward.  One launch each, no workspace, no atomics, nothing filled beforehand, nothing read
+ * back: graph-capturable with the terms' entries between them.
+ * ------------------------------------------------------------------------------------------------ */
+#define GNMS_LOSS_RECORD_COLS 24   /* a ground truth: bbox_full x y w h [0..3], bbox_3d [4..19], class id [20] (1 + index in lbls, 0 for a
+                                      class of ilbls, -1 for neither), ign [21] (0 / not 0), visibility [22], trunc [23] */
+#define GNMS_LOSS_MAX_GTS 256      /* records per image (GNMS_TARGETS_MAX_GTS) */
+#define GNMS_LOSS_STATS 18         /* stats: fg, bg, cls, the after-NMS statistic, bbox_2d, cen, cen_dist_lt_0.2, axis, head, conf, bbox_3d,
+                                      un, z, rot, iou_2d, iou_2d_los, total (the order of the reference's list), the uncertainty weight */
+/* lib/loss/rpn_3d.py:399-419.  records [B][capacity][GNMS_LOSS_RECORD_COLS] float64, counts [B] (clamped to 0..capacity), in the order
+ * the reference iterates the ground truths.  Per record, determine_ignores (rpn_util.py:937-962) as the loss calls it, in float64:
+ * ign = ign | visibility < min_gt_vis | h < min_gt_h | h > max_gt_h (scale_factor 1; the loss leaves max_gt_h at 10e10) | class id == 0
+ * (| trunc > max(1 - min_gt_vis, 0) with use_trunc); rmv = class id < 0.  bbXYWH2Coords: x2 = w + (x - 1), y2 = h + (y - 1).
+ * Outputs, every element written, rows in input order: gts_val [B][capacity][4] / box_lbls [B][capacity] (the class id) / gts_3d
+ * [B][capacity][16] of the records with !rmv & !ign, gts_ign [B][capacity][4] of those with !rmv & ign, val_counts / ign_counts [B];
+ * rows behind a count are zero.  One workgroup per image; 1 <= capacity <= GNMS_LOSS_MAX_GTS (GNMS_ERR_UNSUPPORTED outside).
+ * records, gts_val, gts_3d, gts_ign 16-byte aligned. */
+int gnms_gt_filter(const double* records, const int32_t* counts, int B, int capacity, double min_gt_vis, double min_gt_h,
+                   double max_gt_h, int use_trunc, double* gts_val, int32_t* box_lbls, double* gts_3d, double* gts_ign,
+                   int32_t* val_counts, int32_t* ign_counts, void* stream);
+/* cls_loss [1] / cls_acc [2] of gnms_cls_loss, after_loss = the loss array of gnms_after_nms_finish (phase 1), reg_stats
+ * [GNMS_REG_STATS] / reg_counts [GNMS_REG_STAT_COUNTS] of gnms_reg_loss; a term that is NULL is absent.
+ * total [1] = ((((((0 + cls) + after) + bbox_2d) + bbox_3d) + un) + iou_2d_los) in fp32, the reference's order of `loss +=` (:999,
+ * :1138, :1190, :1371, :1380, :1403), each regression term rounded to fp32 once; the regression terms only with an active anchor
+ * (reg_counts[0] > 0, :1154).  stats [GNMS_LOSS_STATS] float64, every element written (0 for an absent term; the regression
+ * statistics are NaN without an active anchor, as gnms_reg_loss reports them). */
+int gnms_loss_combine(const float* cls_loss, const double* cls_acc, const float* after_loss, const double* reg_stats,
+                      const int32_t* reg_counts, float* total, double* stats, void* stream);
+/* The backward of the whole loss.  upstream [1]: d L / d total on the device.  The terms' dense gradients over rows = B * R anchors:
+ * dcls [rows][C] (gnms_cls_loss), dprob [rows][C] and dacc [rows] (gnms_after_nms_scatter), d2 [rows][4], d3 [rows][D3], da [rows]
+ * (gnms_reg_loss; d3 is zero in the columns the loss does not read); one that is NULL is zero.
+ *   g_cls = upstream * dcls, g_prob = upstream * dprob, g_bbox_2d = upstream * d2, g_bbox_3d = upstream * d3,
+ *   g_acceptance = upstream * (da + dacc)
+ * An output that is NULL is not computed; every element of the others is written (zeros where the inputs are NULL).  All buffers
+ * contiguous float32, 16-byte aligned. */
+int gnms_loss_grad_combine(const float* upstream, long long rows, int C, int D3, const float* dcls, const float* dprob, const float* d2,
+                           const float* d3, const float* da, const float* dacc, float* g_cls, float* g_prob, float* g_bbox_2d,
+                           float* g_bbox_3d, float* g_acceptance, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
