@@ -772,6 +772,31 @@ int gnms_loss_grad_combine(const float* upstream, long long rows, int C, int D3,
                            const float* d3, const float* da, const float* dacc, float* g_cls, float* g_prob, float* g_bbox_2d,
                            float* g_bbox_3d, float* g_acceptance, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The data-set reduction of compute_bbox_stats (lib/rpn_util.py:547-736; csrc/bbox_stats.hip): from the raw
+ * (un-normalised) transforms of gnms_compute_targets to bbox_means / bbox_stds.  One launch each, no workspace, no atomics, nothing
+ * filled beforehand, nothing read back.  Every addition happens in an order the inputs alone fix: the results do not depend on the
+ * batch size, on the order the batches come in, or on the run.
+ * ------------------------------------------------------------------------------------------------ */
+#define GNMS_BBOX_STATS_COLS 13    /* the statistics columns: transforms[:, 0:4] and transforms[:, 5:14] (decomp_alpha) */
+/* transforms [B][R][ld] float32, ld >= 14; image b of the batch is image image_ids[b] (device int32) of a data set of n_images, and
+ * its partials go to that position (an id outside 0..n_images-1: the image writes nothing).  Foreground = transforms[:, 4] > 0
+ * (:629), taken in row order.  counts [n_images] int32: the image's foreground count (both passes).
+ * means NULL, the mean pass: sums [n_images][GNMS_BBOX_STATS_COLS] float32 = np.sum(transforms[fg, cols], axis=0) bit for bit (from
+ * +0, one float32 addition per foreground row in row order; 0 without foreground).
+ * means [GNMS_BBOX_STATS_COLS] float64 on the device, the deviation pass: sq_sums [n_images][GNMS_BBOX_STATS_COLS] float64 = the sum
+ * of (double(x) - mean)^2 in row order.  The other pass's array may be NULL.  One workgroup per image.  B = 0: GNMS_OK, nothing is
+ * done; B > n_images or ld < 14: GNMS_ERR_INVALID_ARGUMENT. */
+int gnms_bbox_stats_partials(const float* transforms, int B, int R, int64_t ld, const int32_t* image_ids, int n_images,
+                             const double* means, float* sums, double* sq_sums, int32_t* counts, void* stream);
+/* The partials of the images with used[i] != 0 (uint8 [n_images]; the others, the images without ground truths of :587, are never
+ * read) and counts[i] > 0, added in image order in double-double, the counts in int64.
+ * deviation = 0: count[0] = the total foreground count; out [GNMS_BBOX_STATS_COLS] = sums / (count + 1e-10) (:579, :652).
+ * deviation = 1: reads count[0] (the mean pass's, :721) and sq_sums; out = sqrt(sq_sums / (count + 1e-10)).
+ * Quotient and root are evaluated in double-double and rounded to float64 once.  Every element of out is written. */
+int gnms_bbox_stats_finish(int deviation, const uint8_t* used, int n_images, const float* sums, const double* sq_sums,
+                           const int32_t* counts, long long* count, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
