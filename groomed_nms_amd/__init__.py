@@ -13,6 +13,7 @@
   groomed_nms_amd.heads         the fifteen maps of the RPN heads -> cls, prob, bbox_2d, bbox_3d, acceptance rows and the anchor tables (models/densenet121_3d_dilate_decomp_alpha.py:166-245)
   groomed_nms_amd.loss          the reference's RPN_3D_loss as one module: ground-truth records -> targets, sampling, the three terms, total, stats list, one-launch backward (lib/loss/rpn_3d.py)
   groomed_nms_amd.dataset_stats the set-up before the first step: generate_anchors (host) and compute_bbox_stats (GPU) -> conf.anchors, conf.bbox_means, conf.bbox_stds (lib/rpn_util.py:24-216, 547-736)
+  groomed_nms_amd.preprocess    the image front end: uint8 BGR images -> mirrored, resized, cropped / padded, normalised float32 RGB planes in one launch; Preprocess, Augmentation (lib/augmentations.py)
   groomed_nms_amd.build         hipcc build of libgroomed_nms_hip.so (C ABI: include/groomed_nms_hip.h)
 """
 from .groomed_nms import (differentiable_nms, differentiable_nms_batched, differentiable_nms_from_boxes_batched, differentiable_nms_with_iou2d_batched, differentiable_nms_with_iou3d_batched, soft_sort, pruning_function, sigmoid_numpy,  # noqa: F401
@@ -34,5 +35,7 @@ from . import loss  # noqa: F401
 from .loss import RPN_3D_loss, pack_ground_truths, GroundTruths  # noqa: F401
 from . import dataset_stats  # noqa: F401
 from .dataset_stats import generate_anchors, compute_bbox_stats  # noqa: F401
+from . import preprocess  # noqa: F401
+from .preprocess import preprocess_images, Preprocess, Augmentation  # noqa: F401
 
 __version__ = "0.1.0"

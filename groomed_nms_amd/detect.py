@@ -280,7 +280,10 @@ def im_detect_3d(im, net, rpn_conf, preprocess, p2, gpu=0, synced=False, return_
     imH_orig = im.shape[0]
     imW_orig = im.shape[1]
     im = preprocess(im)
-    im = torch.from_numpy(im[np.newaxis, :, :, :]).to(dev)                                  # :1074
+    if torch.is_tensor(im):                                                                 # preprocess.Preprocess: already on the device
+        im = im[None].to(dev)
+    else:
+        im = torch.from_numpy(im[np.newaxis, :, :, :]).to(dev)                              # :1074
     imH = im.shape[2]
     scale_factor = imH / imH_orig                                                           # :1079
     cls, prob, bbox_2d, bbox_3d, feat_size, rois, acceptance_prob, acceptance_prob_cls = net(im)   # :1084

@@ -797,6 +797,22 @@ int gnms_bbox_stats_partials(const float* transforms, int B, int R, int64_t ld, 
 int gnms_bbox_stats_finish(int deviation, const uint8_t* used, int n_images, const float* sums, const double* sq_sums,
                            const int32_t* counts, long long* count, double* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The image front end of lib/augmentations.py (Augmentation / Preprocess and the RGB swap + transpose that follow them;
+ * csrc/preprocess.hip): one launch per batch, no workspace, no atomics.
+ * ------------------------------------------------------------------------------------------------ */
+#define GNMS_PREPROCESS_DESC 5     /* int64 per image: byte offset into src, H, W, width after the resize (before crop / pad), mirror */
+/* src: src_bytes of uint8 on the device holding B images, HWC, 3 channels, BGR, each at its descriptor's offset; table [B][5] int64 on
+ * the device; means / stds: 3 floats each ON THE HOST, in the order the reference applies them (entry 0 -> blue), read before the
+ * call returns.  out [B][3][H_out][W_out] float32, RGB planes, 16-byte aligned.  Per output pixel: the source column mirrored when
+ * the flag is set, bilinear taps at (d + 0.5) * (src / dst) - 0.5 (double, rounded to float; floor + fraction, both taps clamped to
+ * the edge; horizontal pass then vertical pass in float32), columns >= the resized width are 0 before the normalisation, then
+ * x / 255, - mean, / std in float32.  H_out is the height after the resize.  Only magnification is meant (src / dst <= 1); the entry
+ * does not check it, the Python wrapper does.  An image whose descriptor does not lie inside src (or with H, W outside 1..2^20) is
+ * not read and its output is not written.  B = 0: GNMS_OK, nothing is done. */
+int gnms_preprocess_images(const uint8_t* src, int64_t src_bytes, const int64_t* table, int B, int H_out, int W_out,
+                           const float* means, const float* stds, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
