@@ -14,6 +14,7 @@
   groomed_nms_amd.loss          the reference's RPN_3D_loss as one module: ground-truth records -> targets, sampling, the three terms, total, stats list, one-launch backward (lib/loss/rpn_3d.py)
   groomed_nms_amd.dataset_stats the set-up before the first step: generate_anchors (host) and compute_bbox_stats (GPU) -> conf.anchors, conf.bbox_means, conf.bbox_stds (lib/rpn_util.py:24-216, 547-736)
   groomed_nms_amd.preprocess    the image front end: uint8 BGR images -> mirrored, resized, cropped / padded, normalised float32 RGB planes in one launch; Preprocess, Augmentation (lib/augmentations.py)
+  groomed_nms_amd.optim         the optimiser side of the loop: lr_schedule / adjust_lr, FusedSGD (clip, SGD with momentum and weight decay, zero_grad and the `loss > 0` gate in one launch per group, capturable), loss_backprop (lib/core.py:99-170)
   groomed_nms_amd.build         hipcc build of libgroomed_nms_hip.so (C ABI: include/groomed_nms_hip.h)
 """
 from .groomed_nms import (differentiable_nms, differentiable_nms_batched, differentiable_nms_from_boxes_batched, differentiable_nms_with_iou2d_batched, differentiable_nms_with_iou3d_batched, soft_sort, pruning_function, sigmoid_numpy,  # noqa: F401
@@ -37,5 +38,7 @@ from . import dataset_stats  # noqa: F401
 from .dataset_stats import generate_anchors, compute_bbox_stats  # noqa: F401
 from . import preprocess  # noqa: F401
 from .preprocess import preprocess_images, Preprocess, Augmentation  # noqa: F401
+from . import optim  # noqa: F401
+from .optim import FusedSGD, lr_schedule  # noqa: F401
 
 __version__ = "0.1.0"

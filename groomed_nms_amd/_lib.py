@@ -160,6 +160,8 @@ _SIGNATURES = {
     "gnms_bbox_stats_finish": (ctypes.c_int, [ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "gnms_preprocess_images": (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float),
                                               ctypes.POINTER(ctypes.c_float), c_vp, c_vp]),
+    "gnms_sgd_step": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                     ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -813,6 +813,27 @@ int gnms_bbox_stats_finish(int deviation, const uint8_t* used, int n_images, con
 int gnms_preprocess_images(const uint8_t* src, int64_t src_bytes, const int64_t* table, int B, int H_out, int W_out,
                            const float* means, const float* stds, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The optimiser step of lib/core.py:99-113 (clip_grad_value_, torch.optim.SGD.step with momentum and weight decay, zero_grad;
+ * csrc/optim.hip): one launch per parameter group, no workspace, no float atomics, nothing read on the host.
+ * ------------------------------------------------------------------------------------------------ */
+#define GNMS_SGD_ROW 4             /* int64 per row of either table */
+/* tensors [n_tensors][4] int64 on the device: the addresses of p, g and buf (float32, contiguous, numel elements each) and numel.
+ * tasks [n_tasks][4] int64 on the device: tensor, start, count, kind; elements start .. start + count - 1 of that tensor.  kind 1: p, g
+ * and buf are 16-byte aligned at `start` (16 bytes per lane, the last count % 4 elements one by one; a task whose addresses are not is
+ * done one by one all the same); kind 0: one by one.  A task that does not lie inside its tensor is skipped.  Every element must lie in
+ * exactly one task.  Per element, in float32, each operation rounded on its own:
+ *     g' = g < -c ? -c : (g > c ? c : g)   (use_clip != 0; NaN stays NaN)      d = g' + f32(weight_decay) * p
+ *     buf = f32(momentum) * buf + d          p = p + f32(-lr) * buf              g = 0
+ * loss: NULL, or a float32 scalar on the device: unless *loss > 0 (so also for NaN) p and buf are left as they are and g is zeroed.
+ * lr_table: NULL (lr is the argument), or lr_table_len float64 on the device: lr = lr_table[min(max(state[0], 0), lr_table_len - 1)].
+ * state: int64 [2] on the device, {iteration, 0}.  advance != 0: the launch adds 1 to state[0] after every workgroup has read it
+ * (state[1] is the ticket they take, 0 again when the launch ends).  grid: workgroups, 0 = four per compute unit; nt: bit 0 = the 16-byte
+ * loads non-temporal, bit 1 = the 16-byte stores (0..3; the same values either way).  n_tasks = 0: only the counter moves. */
+int gnms_sgd_step(const int64_t* tensors, int n_tensors, const int64_t* tasks, int n_tasks, double lr, double momentum,
+                  double weight_decay, double clip_value, int use_clip, const float* loss, const double* lr_table, int lr_table_len,
+                  int64_t* state, int advance, int grid, int nt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

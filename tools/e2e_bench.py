@@ -113,6 +113,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=1760)
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "fused"],
+                    help="torch: torch.optim.SGD (the numbers on record); fused: groomed_nms_amd.optim.FusedSGD, clip + update + zero_grad in one launch")
     args = ap.parse_args()
     from groomed_nms_amd import dist as gdist
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -133,7 +135,11 @@ def main():
     model = net
     if torch.distributed.is_initialized():
         model = nn.parallel.DistributedDataParallel(net, device_ids=[local_rank], bucket_cap_mb=25)     # RCCL all-reduce, overlapped with backward
-    opt = torch.optim.SGD(net.parameters(), lr=1e-4, momentum=0.9)
+    if args.optimizer == "fused":
+        from groomed_nms_amd.optim import FusedSGD
+        opt = FusedSGD(net.parameters(), lr=1e-4, momentum=0.9, clip_value=None)          # no clip: the same update as torch's below
+    else:
+        opt = torch.optim.SGD(net.parameters(), lr=1e-4, momentum=0.9)
     img = torch.randn((B, 3, args.height, args.width), device=dev)
     rng = np.random.default_rng(7 + rank)
 
@@ -166,9 +172,14 @@ def main():
         targets, _, _ = PR.best_targets(p3, b_sel, gt3d, gt2d, 0.0, num, None)
         # + a stand-in for the box-regression terms of the reference's loss (lib/loss/rpn_3d.py), so that every head receives a gradient
         loss = ap_loss_batched(out[0], targets, counts=num).mean() + 1e-3 * (d2.square().mean() + d3.square().mean())
-        opt.zero_grad(set_to_none=True)
-        loss.backward()
-        opt.step()
+        if args.optimizer == "fused":
+            opt.zero_grad()                              # keeps the tensors (set_to_none moves them: the tables are rebuilt every step); launches nothing
+            loss.backward()
+            opt.step(loss=loss)                                                           # `if loss > 0` on the device
+        else:
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
         del t0
         return loss.detach()
 
@@ -213,7 +224,7 @@ def main():
             "value": round(imgs / dt, 2), "unit": "images/s", "n_gpus": world, "ms_per_step": round(dt / args.steps * 1e3, 3),
             "boxes_into_nms_per_s": round(imgs * K / dt, 1),
             "config": {"model": "DenseNet-121 RPN-3D (random init, %.1f M parameters, fp32)" % (n_params / 1e6), "image": [3, args.height, args.width],
-                       "images_per_gpu": B, "anchors_per_image": int(anchors.shape[0]), "proposals_into_nms": K,
+                       "optimizer": args.optimizer, "images_per_gpu": B, "anchors_per_image": int(anchors.shape[0]), "proposals_into_nms": K,
                        "parallelism": "dp%d%s" % (world, " (DDP, RCCL all-reduce of %.0f MB fp32 gradients per step)" % (n_params * 4 / 1e6) if world > 1 or torch.distributed.is_initialized() else "")},
             "split_ms": {"whole_step": round(dt / args.steps * 1e3, 3), "decode_topk_iou_nms%s" % ("_bwd" if train else ""): round(phase["nms_path"] * 1e3, 3)},
             "data": "synthetic", "last_loss_or_nvalid": [float(x) for x in last.flatten().tolist()][:4]}))
