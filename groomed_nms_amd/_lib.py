@@ -33,6 +33,9 @@ _SIGNATURES = {
     "gnms_last_error": (ctypes.c_char_p, []),
     "gnms_default_params": (None, [ctypes.POINTER(GnmsParams)]),
     "gnms_iou2d": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int64, c_vp]),
+    "gnms_iou2d_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "gnms_iou2d_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, c_vp, c_vp,
+                                           ctypes.c_size_t, c_vp]),
     "gnms_corners_of_cuboid": (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, c_vp]),
     "gnms_iou2d_f64": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int64, c_vp]),
     "gnms_corners_of_cuboid_f64": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
@@ -63,6 +66,10 @@ _SIGNATURES = {
                                                c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "gnms_backward_from_boxes": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.POINTER(GnmsParams), c_vp,
                                                 c_vp, ctypes.c_size_t, c_vp]),
+    "gnms_backward_boxes_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(GnmsParams), ctypes.c_int,
+                                                            ctypes.c_int]),
+    "gnms_backward_boxes": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.POINTER(GnmsParams), c_vp, c_vp, c_vp,
+                                           ctypes.c_int64, ctypes.c_int, c_vp, ctypes.c_size_t, c_vp, ctypes.c_size_t, c_vp]),
     "gnms_profile_bitmask": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, ctypes.c_float, c_vp,
                                             ctypes.c_size_t, c_vp]),
     "gnms_profile_bitmask_boxes": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_float, c_vp, ctypes.c_size_t, c_vp]),

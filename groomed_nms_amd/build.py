@@ -8,8 +8,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libgroomed_nms_hip.so")
-SOURCES = ["iou_kernels.hip", "nms_layer.hip", "soft_sort.hip", "classic_nms.hip", "nms_others.hip", "aploss.hip", "proposals.hip", "host_mailbox.hip", "iou3d_exact.hip", "targets.hip", "detect3d.hip", "kitti_eval.hip", "kitti_rows.hip", "sampling.hip", "regression.hip", "after_nms.hip", "heads.hip", "loss.hip", "bbox_stats.hip", "preprocess.hip", "optim.hip"]
-HEADERS = ["gnms_common.h", "bbox_decode.h", "gnms_prof.h", "iou_tile.h", "cuboid_corners.h", "bev_clip.h", "iou3d_pair.h", "iou3d_tile.h", "iou3d_sym.h", "gnms_device.h", "sort_bins.h", "nms_sort_kernels.h", "nms_scan_kernels.h", "nms_kernels.h", "nms_one_launch.h", "nms_backward_kernels.h", "nms_solve_kernels.h",
+SOURCES = ["iou_kernels.hip", "nms_layer.hip", "soft_sort.hip", "classic_nms.hip", "nms_others.hip", "aploss.hip", "proposals.hip", "host_mailbox.hip", "iou3d_exact.hip", "targets.hip", "detect3d.hip", "kitti_eval.hip", "kitti_rows.hip", "sampling.hip", "regression.hip", "after_nms.hip", "heads.hip", "loss.hip", "bbox_stats.hip", "preprocess.hip", "optim.hip", "iou_backward.hip"]
+HEADERS = ["gnms_common.h", "bbox_decode.h", "gnms_prof.h", "iou_tile.h", "iou_grad.h", "cuboid_corners.h", "bev_clip.h", "iou3d_pair.h", "iou3d_tile.h", "iou3d_sym.h", "gnms_device.h", "sort_bins.h", "nms_sort_kernels.h", "nms_scan_kernels.h", "nms_kernels.h", "nms_one_launch.h", "nms_backward_kernels.h", "nms_solve_kernels.h",
            os.path.join("..", "..", "include", "groomed_nms_hip.h")]
 # -ffp-contract=off: products and sums round separately, like the reference's torch CPU kernels
 # (lib/core.py:499-508) -- this is what makes the overlap matrices bit-identical.

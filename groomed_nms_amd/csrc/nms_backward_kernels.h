@@ -11,6 +11,7 @@
 // Everything is gather-form and deterministic (no float atomics): bit-identical run to run.
 #pragma once
 #include "nms_kernels.h"
+#include "iou_grad.h"
 
 namespace gnms {
 
@@ -228,6 +229,80 @@ __global__ __launch_bounds__(256) void bwd_masked_iou_kernel(const float* __rest
     const size_t e = (size_t)b * N * ld + (size_t)ck * ld + ch;
     const float d = gnms_prune_grad(iou[e], P.nms_threshold, P.temperature, P.pruning_method);
     grad_iou[e] = (-(I.gx[q] * I.sscore[h])) * d;
+}
+
+// dL/dboxes of the masked-group layer (hard sort, unsorted output: bwd_masked_fused_kernel's / bwd_plan_kernel's modes) WITHOUT an N x N
+// pass: the layer's matrix gradient has one entry per non-head member k, at [member][head] (bwd_masked_iou_kernel), so
+//   member k : dL/dbox_k    = g_k * dIoU(box_k, box_head)/da          one term, a plain store
+//   head h   : dL/dbox_h    = sum_k g_k * dIoU(box_k, box_h)/db       sequentially in member order over the group's run
+//   g_k = (-(gx_k s_h)) f'(IoU(box_k, box_h)), the IoU recomputed from the boxes with the forward's operation order
+// ONE launch with bwd_masked_fused_kernel's two kinds of workgroups: blockIdx.x < elem_blocks, one thread per rank (members; 0 for
+// boxes in no group, heads without members and boxes behind counts[b]); above, one WAVE per multi-member group (hlist): the lanes fetch
+// the members' terms in parallel, the four sums then run SEQUENTIALLY in member order (v_readlane + v_add), as dL/ds_head does.
+// The pair arithmetic is iou_grad.h's, with the member as the row box, exactly as gnms_iou2d_backward evaluates the same entry: a
+// member's gradient is the same bits on both routes.  Indices out of the workspace are clamped to the image.
+__device__ __forceinline__ float bwd_member_cotangent(const float* __restrict__ gp, const ImgPtrs& I, int k, int h, const gnms_iou_grad::Pair& p,
+                                                      const gnms_params& P) {
+    const float d = gnms_prune_grad(p.inter / p.uni, P.nms_threshold, P.temperature, P.pruning_method);
+    return (-(bwd_gx_of(gp, I, k) * I.sscore[h])) * d;
+}
+
+__global__ __launch_bounds__(256) void bwd_masked_boxes_kernel(const float* __restrict__ grad_prob, const float* __restrict__ boxes, int N,
+                                                               const int* __restrict__ counts, gnms_params P, char* ws, gnms_ws_layout L,
+                                                               float* __restrict__ grad_boxes, int elem_blocks) {
+    using namespace gnms_iou_grad;
+    const int b = blockIdx.y;
+    const int n = gnms_count(counts, b, N);
+    ImgPtrs I = img_ptrs(ws, L, b);
+    const float4* bx = reinterpret_cast<const float4*>(boxes) + (size_t)b * N;
+    float4* gb = reinterpret_cast<float4*>(grad_boxes) + (size_t)b * N;
+    const float* gp = grad_prob + (size_t)b * N;
+    const unsigned last = (unsigned)(n > 0 ? n - 1 : 0);
+    if ((int)blockIdx.x >= elem_blocks) {
+        if (n == 0) return;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int nheads = min(I.misc[1], n);
+        const int nhb = (int)gridDim.x - elem_blocks;
+        for (int hi = ((int)blockIdx.x - elem_blocks) * 4 + wave; hi < nheads; hi += nhb * 4) {
+            const int k = (int)min((unsigned)I.hlist[hi], last);
+            const int hstart = I.gstart[k], hlen = I.glen[k];
+            if (hstart < 0 || hlen < 2 || hstart + hlen > n) continue;                    // (a workspace the forward never filled)
+            const int ck = (int)min((unsigned)I.order[k], last);
+            const float4 hb = bx[ck];
+            const float harea = box_area(hb);
+            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int base = 1; base < hlen; base += 64) {
+                const int t = base + lane;
+                float term[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (t < hlen) {
+                    const int mk = (int)min((unsigned)I.gsorted[hstart + t], last);
+                    const float4 a = bx[min((unsigned)I.order[mk], last)];
+                    const Pair p = pair_of(a, box_area(a), hb, harea);
+                    add_box_grad(hb, a, p, bwd_member_cotangent(gp, I, mk, k, p, P), term);
+                }
+                const int cnt = min(64, hlen - base);
+                for (int u = 0; u < cnt; ++u) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) acc[c] += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(term[c]), u));
+                }
+            }
+            if (lane == 0) gb[ck] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        }
+        return;
+    }
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= N) return;
+    if (k >= n) { gb[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); return; }
+    const int ck = (int)min((unsigned)I.order[k], last);
+    const int h = I.head[k];
+    if (h == k && I.glen[k] > 1 && I.misc[1] > 0) return;            // written by the head waves (hlist holds exactly these)
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (h >= 0 && h != k && h < n) {
+        const float4 a = bx[ck], hb = bx[min((unsigned)I.order[h], last)];
+        const Pair p = pair_of(a, box_area(a), hb, box_area(hb));
+        add_box_grad(a, hb, p, bwd_member_cotangent(gp, I, k, h, p, P), acc);
+    }
+    gb[ck] = make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
 
 }  // namespace gnms

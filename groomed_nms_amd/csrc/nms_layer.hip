@@ -1847,6 +1847,67 @@ extern "C" int gnms_backward_from_boxes(const float* grad_prob, const float* box
     return launch_solve_groups<kBackward, kFromBoxes>(c, boxes, N, grad_scores, nullptr);
 }
 
+// ------------------------------------------------------------------------------------------------
+// backward with the gradient w.r.t. the boxes
+// ------------------------------------------------------------------------------------------------
+namespace {
+// masked groups, hard sort, unsorted output: one matrix-gradient entry per non-head member, no N x N pass
+bool boxes_sparse_route(const gnms_params& P, int route) {
+    return route == GNMS_BOXES_ROUTE_AUTO && P.group_boxes && P.mask_group_boxes && !P.return_sorted_prob && !P.presorted;
+}
+struct BoxesScratch { size_t grad_iou, iou, reduce, total; };
+BoxesScratch boxes_scratch(int B, int N, int64_t ld, bool have_iou) {
+    BoxesScratch s;
+    s.grad_iou = gnms_align_up(sizeof(float) * (size_t)B * N * ld, 256);
+    s.iou = have_iou ? 0 : s.grad_iou;
+    s.reduce = gnms_iou2d_backward_workspace_bytes(B, N, N);
+    s.total = s.grad_iou + s.iou + s.reduce;
+    return s;
+}
+}  // namespace
+
+extern "C" size_t gnms_backward_boxes_scratch_bytes(int B, int N, int64_t ld, const gnms_params* params, int have_iou, int route) {
+    if (!params || B <= 0 || N <= 0 || ld < N || boxes_sparse_route(*params, route)) return 0;
+    return boxes_scratch(B, N, ld, have_iou != 0).total;
+}
+
+extern "C" int gnms_backward_boxes(const float* grad_prob, const float* boxes, const float* scores, int B, int N, const int32_t* counts,
+                                   const gnms_params* params, float* grad_scores, float* grad_boxes, const float* iou, int64_t ld, int route,
+                                   void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    LayerCall c;
+    GNMS_CHECK_ARG(route == GNMS_BOXES_ROUTE_AUTO || route == GNMS_BOXES_ROUTE_DENSE, "gnms_backward_boxes: unknown route %d", route);
+    GNMS_BEGIN_CALL("gnms_backward_boxes", &c, B, N, ld, counts, params, workspace, workspace_bytes, stream, false,
+                    grad_prob && boxes && scores && grad_scores && grad_boxes, "gnms_backward_boxes: null pointer");
+    GNMS_CHECK_ARG(((uintptr_t)boxes % 16 == 0) && ((uintptr_t)grad_boxes % 16 == 0), "gnms_backward_boxes: boxes and grad_boxes must be 16-byte aligned");
+    if (boxes_sparse_route(c.P, route)) {
+        // (the masked backward never dereferences the matrix pointer when no matrix gradient is asked for)
+        const int rc = gnms_backward(grad_prob, scores, boxes, B, N, N, counts, params, grad_scores, nullptr, workspace, workspace_bytes, stream);
+        if (rc) return rc;
+        const int elem_blocks = gnms_div_up(N, 256), head_blocks = N >= 2048 ? 128 : gnms_div_up(N, 16);
+        bwd_masked_boxes_kernel<<<dim3(elem_blocks + head_blocks, B), 256, 0, c.st>>>(grad_prob, boxes, N, counts, c.P, c.ws, c.L, grad_boxes,
+                                                                                      elem_blocks);
+        GNMS_CHECK_LAUNCH();
+        return GNMS_OK;
+    }
+    // every other mode: the layer's matrix gradient into the scratch matrix, then gnms_iou2d_backward with the boxes on both sides
+    const BoxesScratch s = boxes_scratch(B, N, ld, iou != nullptr);
+    GNMS_CHECK_ARG(scratch != nullptr && (uintptr_t)scratch % 256 == 0, "gnms_backward_boxes: scratch is NULL or not 256-byte aligned");
+    if (scratch_bytes < s.total) {
+        gnms_set_error("gnms_backward_boxes: scratch too small (%zu < %zu)", scratch_bytes, s.total);
+        return GNMS_ERR_WORKSPACE;
+    }
+    float* grad_iou = static_cast<float*>(scratch);
+    int rc;
+    if (!iou) {
+        float* m = reinterpret_cast<float*>(static_cast<char*>(scratch) + s.grad_iou);
+        if ((rc = gnms_iou2d(boxes, boxes, B, N, N, m, ld, stream))) return rc;
+        iou = m;
+    }
+    if ((rc = gnms_backward(grad_prob, scores, iou, B, N, ld, counts, params, grad_scores, grad_iou, workspace, workspace_bytes, stream))) return rc;
+    return gnms_iou2d_backward(boxes, nullptr, grad_iou, B, N, N, ld, grad_boxes, nullptr, static_cast<char*>(scratch) + s.grad_iou + s.iou, s.reduce,
+                               stream);
+}
+
 // Profiling hook: re-runs ONLY the threshold bit-matrix kernel (K2, the one full read of the matrix) on a
 // workspace that a previous gnms_forward filled (it needs `order`).  bench.py times it for the roofline line.
 extern "C" int gnms_profile_bitmask(const float* iou, int B, int N, int64_t ld, const int32_t* counts, float nms_threshold,

@@ -282,6 +282,85 @@ class _GroomedNMSFromBoxesFunction(torch.autograd.Function):
         return grad_scores, None, None, None
 
 
+# Developer / test switch for the backward of _GroomedNMSBoxGradFunction: "auto" (the library picks: the sparse route for masked groups,
+# hard sort, unsorted output; the dense route elsewhere) or "dense" (the matrix gradient + gnms_iou2d_backward in every mode).  A call reads
+# it once, in its forward, and its backward takes that route whatever the switch says by then.
+BOX_GRAD_ROUTE = "auto"
+_BOX_ROUTES = {"auto": 0, "dense": 1}
+
+
+class _GroomedNMSBoxGradFunction(torch.autograd.Function):
+    """The two one-call 2D entries when `boxes` requires grad: the forwards of _GroomedNMSWithIouFunction (with_matrix) and
+    _GroomedNMSFromBoxesFunction, and a backward that also returns dL/dboxes (gnms_backward_boxes) -- what autograd gives
+    the reference for differentiable_nms(scores, iou(boxes, boxes)) when the caller does not detach the overlaps.  The returned
+    matrix of the with-matrix entry stays non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, scores, boxes, counts, params, iou_out, with_matrix):
+        lib = _lib.load()
+        B, N = scores.shape
+        dev = scores.device
+        scores_c = scores.contiguous()
+        boxes_c = boxes.contiguous()
+        aligned = boxes_c.data_ptr() % 16 == 0
+        # (the kernels load a box as one float4; without a box gradient an unaligned view is refused by gnms_iou2d -- here it is copied)
+        boxes_al = boxes_c if aligned else boxes_c.clone()
+        prob, order, valid, invalid, nvalid, ninvalid = _outputs(B, N, dev, getattr(params, "index_lists", True))
+        ws = torch.empty((max(_workspace_bytes(lib, B, N, params), 256),), dtype=torch.uint8, device=dev)
+        iou = None
+        with on_device(dev):
+            if with_matrix:
+                iou = iou_out if iou_out is not None else torch.empty((B, N, N), dtype=torch.float32, device=dev)
+                check(lib.gnms_forward_with_iou2d(ptr(boxes_al), ptr(scores_c), B, N, max(N, 1), ptr(counts), ctypes.byref(params), ptr(iou),
+                                                  ptr(prob), ptr(order), ptr(valid), ptr(invalid), ptr(nvalid), ptr(ninvalid), ptr(ws),
+                                                  ws.numel(), stream_ptr(dev)), "gnms_forward_with_iou2d")
+            else:
+                check(lib.gnms_forward_from_boxes(ptr(boxes_al), ptr(scores_c), B, N, ptr(counts), ctypes.byref(params), ptr(prob), ptr(order),
+                                                  ptr(valid), ptr(invalid), ptr(nvalid), ptr(ninvalid), ptr(ws), ws.numel(), stream_ptr(dev)),
+                      "gnms_forward_from_boxes")
+        ctx.params = params
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*[x for x in (order, valid, invalid, nvalid, ninvalid, iou) if x is not None])
+        # the matrix is kept (through autograd: its version counter catches a caller that overwrites `iou_out`) only where the backward
+        # will read it: the dense route.  The sparse route recomputes its one overlap per member from the boxes.
+        ctx.route = _BOX_ROUTES[BOX_GRAD_ROUTE]                     # read ONCE per call, here: the backward takes the route the forward planned for
+        sparse = (ctx.route == 0 and params.group_boxes and params.mask_group_boxes and not params.return_sorted_prob
+                  and not params.presorted)                         # (gnms_backward_boxes' own test, nms_layer.hip boxes_sparse_route)
+        ctx.has_iou = iou is not None and not sparse
+        if ctx.has_iou:
+            ctx.save_for_backward(scores_c, boxes_al, counts, ws, iou)
+        else:
+            ctx.save_for_backward(scores_c, boxes_al, counts, ws)
+        if with_matrix:
+            return prob, order, valid, invalid, nvalid, ninvalid, iou
+        return prob, order, valid, invalid, nvalid, ninvalid
+
+    @staticmethod
+    def backward(ctx, grad_prob, *unused):
+        if grad_prob is None:
+            return None, None, None, None, None, None
+        lib = _lib.load()
+        if ctx.has_iou:
+            scores_c, boxes_al, counts, ws, iou = ctx.saved_tensors
+        else:
+            scores_c, boxes_al, counts, ws = ctx.saved_tensors
+            iou = None
+        B, N = scores_c.shape
+        dev = scores_c.device
+        grad_prob = grad_prob.contiguous().float()
+        grad_scores = torch.empty_like(scores_c)
+        grad_boxes = torch.empty_like(boxes_al)
+        route = ctx.route
+        ld = max(N, 1)
+        nbytes = lib.gnms_backward_boxes_scratch_bytes(B, N, ld, ctypes.byref(ctx.params), int(iou is not None), route)
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+        with on_device(dev):
+            check(lib.gnms_backward_boxes(ptr(grad_prob), ptr(boxes_al), ptr(scores_c), B, N, ptr(counts), ctypes.byref(ctx.params),
+                                          ptr(grad_scores), ptr(grad_boxes), ptr(iou), ld, route, ptr(scratch), nbytes, ptr(ws), ws.numel(),
+                                          stream_ptr(dev)), "gnms_backward_boxes")
+        return grad_scores, grad_boxes, None, None, None, None
+
+
 class _SoftSortFunction(torch.autograd.Function):
     """soft_sort (lib/groomed_nms.py:131-165) for one image: HIP forward (row kernels + fp32 MFMA GEMM) and HIP backward
     (gnms_soft_sort_backward: the hand-derived adjoint of the same expressions, including the reference's last-axis
@@ -419,6 +498,8 @@ def differentiable_nms_with_iou2d_batched(scores, boxes, counts=None, iou_out=No
                      mask_group_boxes, group_size, False, bool(index_lists))
     if counts is not None:
         counts = counts.to(device=scores.device, dtype=torch.int32).contiguous()
+    if boxes.requires_grad and torch.is_grad_enabled():              # dL/dboxes as well; without it the calls below, unchanged
+        return _GroomedNMSBoxGradFunction.apply(scores.float(), boxes.float(), counts, params, iou_out, True)
     ext = _binding()
     if ext and scores.is_cuda:
         return tuple(_layer(ext, scores.float(), boxes.float(), counts, iou_out, _MODE_IOU2D, params))
@@ -453,6 +534,8 @@ def differentiable_nms_from_boxes_batched(scores, boxes, counts=None, nms_thresh
                      mask_group_boxes, group_size, False, bool(index_lists))
     if counts is not None:
         counts = counts.to(device=scores.device, dtype=torch.int32).contiguous()
+    if boxes.requires_grad and torch.is_grad_enabled():              # dL/dboxes as well; without it the calls below, unchanged
+        return _GroomedNMSBoxGradFunction.apply(scores.float(), boxes.float(), counts, params, None, False)
     ext = _binding()
     if ext and scores.is_cuda:
         return tuple(_layer(ext, scores.float(), boxes.float(), counts, None, _MODE_BOXES, params)[:6])

@@ -28,10 +28,12 @@ def _is_f64_array(x):
     return isinstance(x, np.ndarray) and x.dtype == np.float64
 
 
-def _to_dev(x):
+def _to_dev(x, keep_grad=False):
     if isinstance(x, np.ndarray):
         return torch.from_numpy(np.ascontiguousarray(x)).to(device=_device(), dtype=torch.float32), "numpy", None
     dev = x.device if x.device.type == "cuda" else _device()
+    if keep_grad and x.requires_grad and torch.is_grad_enabled():       # (iou: the moves are differentiable, the gradient flows back to `x`)
+        return x.to(device=dev, dtype=torch.float32), "torch", x.device
     return x.detach().to(device=dev, dtype=torch.float32), "torch", x.device
 
 
@@ -41,8 +43,62 @@ def _back(t, kind, device):
     return t.to(device)
 
 
+def _aligned(t):
+    """`t` contiguous and 16-byte aligned (the kernels load a box as one float4): itself where it already is"""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _cotangent_layout(grad, B, M, N):
+    """(tensor, ld) for a cotangent [B, M, N] of a RECTANGULAR overlap matrix as gnms_iou2d_backward reads it: unit column stride, row
+    stride ld >= N, image stride M * ld.  A view that already lies so (a slice of a wider buffer) is used where it is; anything else
+    (a transpose, an expanded tensor) is copied once.  (groomed_nms._matrix_layout is the square [B, N, N] form of this.)"""
+    assert tuple(grad.shape) == (B, M, N)
+    if B == 0 or M == 0 or N == 0:
+        return grad.contiguous(), max(N, 1)
+    ld = grad.stride(1)
+    if grad.stride(2) == 1 and ld >= N and grad.stride(0) == M * ld:
+        return grad, ld
+    return grad.contiguous(), N          # (also where a size-1 dimension carries an arbitrary stride: the copy is then free)
+
+
+class _Iou2dFunction(torch.autograd.Function):
+    """iou_batched with the gradient w.r.t. the boxes: the forward is the same gnms_iou2d launch, the backward is
+    gnms_iou2d_backward (csrc/iou_backward.hip) -- the reference's iou() is a few torch operations that autograd differentiates
+    (lib/core.py:499-508); this is that derivative in closed form.  boxes_b None: boxes_a on both sides."""
+
+    @staticmethod
+    def forward(ctx, boxes_a, boxes_b):
+        a = _aligned(boxes_a)
+        b = None if boxes_b is None else _aligned(boxes_b)
+        ctx.save_for_backward(a, b)
+        return iou_batched(a.detach(), None if b is None else b.detach())
+
+    @staticmethod
+    def backward(ctx, grad):
+        a, b = ctx.saved_tensors
+        lib = _lib.load()
+        B, M, _ = a.shape
+        N = M if b is None else b.shape[1]
+        grad, ld = _cotangent_layout(grad.float(), B, M, N)
+        d_a = torch.empty_like(a) if (b is None or ctx.needs_input_grad[0]) else None
+        d_b = torch.empty_like(b) if (b is not None and ctx.needs_input_grad[1]) else None
+        ws = torch.empty((max(lib.gnms_iou2d_backward_workspace_bytes(B, M, N), 256),), dtype=torch.uint8, device=a.device)
+        with on_device(a.device):
+            check(lib.gnms_iou2d_backward(ptr(a), ptr(b), ptr(grad), B, M, N, ld, ptr(d_a), ptr(d_b), ptr(ws), ws.numel(),
+                                          stream_ptr(a.device)), "gnms_iou2d_backward")
+        return d_a, d_b
+
+
 def iou_batched(boxes_a, boxes_b=None, out=None):
-    """boxes_a [B,M,4], boxes_b [B,N,4] (CUDA fp32) -> [B,M,N].  boxes_b=None means boxes_a."""
+    """boxes_a [B,M,4], boxes_b [B,N,4] (CUDA fp32) -> [B,M,N].  boxes_b=None means boxes_a.  Differentiable w.r.t. the boxes: when
+    one of them requires grad the result carries a grad_fn (gnms_iou2d_backward); otherwise it is a leaf, the same call as ever."""
+    if torch.is_grad_enabled() and (boxes_a.requires_grad or (boxes_b is not None and boxes_b.requires_grad)):
+        if out is not None:
+            raise ValueError("iou_batched: `out` cannot be given when the boxes require grad")
+        if not boxes_a.is_cuda or boxes_a.dtype != torch.float32 or (boxes_b is not None and boxes_b.dtype != torch.float32):
+            raise TypeError("iou_batched: the gradient w.r.t. the boxes needs CUDA float32 boxes")
+        return _Iou2dFunction.apply(boxes_a, None if boxes_b is boxes_a else boxes_b)
     from .groomed_nms import _binding
     ext = _binding()
     if ext and boxes_a.is_cuda and boxes_a.dtype == torch.float32 and (boxes_b is None or boxes_b.dtype == torch.float32):
@@ -121,13 +177,16 @@ def iou(box_a, box_b, mode='combinations', data_type=None):
             with on_device(dev):
                 check(lib.gnms_iou2d_f64(ptr(a), ptr(b), 1, M, N, ptr(out), max(N, 1), stream_ptr(dev)), "gnms_iou2d_f64")
             return out.cpu().numpy()
-        a, kind, dev = _to_dev(box_a)
-        b, _, _ = _to_dev(box_b)
-        out = iou_batched(a[:, :4].unsqueeze(0), b[:, :4].unsqueeze(0))[0]
+        a, kind, dev = _to_dev(box_a, keep_grad=True)
+        b = a if (box_b is box_a and a.requires_grad) else _to_dev(box_b, keep_grad=True)[0]
+        av = a[:, :4].unsqueeze(0)
+        # (iou(x, x) on one tensor: the same view on both sides, so that the gradient takes the one-box-set form of gnms_iou2d_backward)
+        out = iou_batched(av, av if b is a else b[:, :4].unsqueeze(0))[0]
         return _back(out, kind, dev)
     if mode == 'list':
-        a, kind, dev = _to_dev(box_a)
-        b, _, _ = _to_dev(box_b)
+        # (torch arithmetic: differentiable w.r.t. the boxes like the reference's own expression)
+        a, kind, dev = _to_dev(box_a, keep_grad=True)
+        b, _, _ = _to_dev(box_b, keep_grad=True)
         max_xy = torch.min(a[:, 2:4], b[:, 2:4])
         min_xy = torch.max(a[:, 0:2], b[:, 0:2])
         wh = torch.clamp(max_xy - min_xy, 0)

@@ -83,6 +83,18 @@ const char* gnms_last_error(void);
  * No +1 pixel; a zero-area pair yields 0/0 = NaN exactly like the reference. */
 int gnms_iou2d(const float* boxes_a, const float* boxes_b, int B, int M, int N, float* out, int64_t ld, void* stream);
 
+/* backward of gnms_iou2d: the cotangent grad [B][M][ld] of the matrix contracted with dIoU/dbox (torch autograd's conventions for
+ * lib/core.py:499-508: a tied max / min splits its gradient evenly, the clamp passes it at 0).
+ *   d_boxes_a [B][M][4] = sum_j grad[i][j] dIoU(a_i, b_j)/da_i,  d_boxes_b [B][N][4] = sum_i grad[i][j] dIoU(a_i, b_j)/db_j.
+ * Either output may be NULL (not both).  boxes_b == NULL means boxes_a on both sides (M == N): both roles are summed into d_boxes_a,
+ * d_boxes_b must be NULL.  Every element of a given output is written.  A pair whose cotangent is exactly 0 contributes nothing
+ * (torch: 0 * NaN for a zero-area pair); everything else is plain IEEE fp32.  grad is read once; the sums go through per-tile partial
+ * slabs in `workspace` (gnms_iou2d_backward_workspace_bytes(B, M, N) bytes, 256-byte aligned) added in a fixed order: no float
+ * atomics, the same inputs give the same bits.  Stream-ordered, no allocation, graph-capturable. */
+size_t gnms_iou2d_backward_workspace_bytes(int B, int M, int N);
+int gnms_iou2d_backward(const float* boxes_a, const float* boxes_b, const float* grad, int B, int M, int N, int64_t ld, float* d_boxes_a,
+                        float* d_boxes_b, void* workspace, size_t workspace_bytes, void* stream);
+
 /* get_corners_of_cuboid  lib/math_3d.py:364-435 (torch branch, iou_3d_convention=True).
  * params [count][7] = (x3d, y3d, z3d, w3d, h3d, l3d, ry3d) -> corners [count][3][8]. */
 int gnms_corners_of_cuboid(const float* params, int64_t count, float* corners, void* stream);
@@ -234,6 +246,25 @@ int gnms_forward_from_boxes(const float* boxes, const float* scores, int B, int 
 int gnms_backward_from_boxes(const float* grad_prob, const float* boxes, const float* scores, int B, int N,
                              const int32_t* counts, const gnms_params* params, float* grad_scores, void* workspace,
                              size_t workspace_bytes, void* stream);
+
+/* backward of L through prob WITH the gradient w.r.t. the 2D boxes the overlaps were computed from (iou = gnms_iou2d(boxes, boxes)):
+ * what autograd gives the reference for differentiable_nms(scores, iou(boxes, boxes)) when the caller does not detach.  Pairs with
+ * every 2D forward entry (gnms_forward on that matrix, gnms_forward_with_iou2d, gnms_forward_from_boxes); scores / counts / params /
+ * workspace must be the ones the forward call saw.
+ *   grad_scores [B][N], grad_boxes [B][N][4] (input order), both fully overwritten; boxes behind counts[b] and boxes in no group get 0.
+ *   iou         the forward's matrix [B][N][ld], or NULL: the dense route then rebuilds it in `scratch` (ld is its row stride there too).
+ *   route       GNMS_BOXES_ROUTE_AUTO: masked groups, hard sort, unsorted output (the default mode) take the SPARSE route -- the matrix
+ *               gradient has one entry per non-head member, so the members' and heads' box gradients come out of one O(N) launch
+ *               behind gnms_backward's, no N x N pass, no scratch, `iou` not read.  Every other mode, and GNMS_BOXES_ROUTE_DENSE for
+ *               any mode: gnms_backward with grad_iou written into `scratch`, then gnms_iou2d_backward with the boxes on both sides.
+ *   scratch     gnms_backward_boxes_scratch_bytes(B, N, ld, params, iou != NULL, route) bytes, 256-byte aligned (0 on the sparse route).
+ * A non-head member's gradient is the same bits on both routes (one term); a head's is a sum in member order on the sparse route. */
+#define GNMS_BOXES_ROUTE_AUTO 0
+#define GNMS_BOXES_ROUTE_DENSE 1
+size_t gnms_backward_boxes_scratch_bytes(int B, int N, int64_t ld, const gnms_params* params, int have_iou, int route);
+int gnms_backward_boxes(const float* grad_prob, const float* boxes, const float* scores, int B, int N, const int32_t* counts,
+                        const gnms_params* params, float* grad_scores, float* grad_boxes, const float* iou, int64_t ld, int route,
+                        void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
 /* profiling hook: re-runs only the threshold bit-matrix kernel (the single full read of the overlap matrix, the
  * dominant kernel of gnms_forward) on a workspace a previous gnms_forward call filled. */
