@@ -8,9 +8,10 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libgroomed_nms_hip.so")
-SOURCES = ["iou_kernels.hip", "nms_layer.hip", "soft_sort.hip", "classic_nms.hip", "nms_others.hip", "aploss.hip", "proposals.hip", "host_mailbox.hip", "iou3d_exact.hip", "targets.hip", "detect3d.hip", "kitti_eval.hip", "kitti_rows.hip", "sampling.hip", "regression.hip", "after_nms.hip", "heads.hip", "loss.hip", "bbox_stats.hip", "preprocess.hip", "optim.hip", "iou_backward.hip"]
-HEADERS = ["gnms_common.h", "bbox_decode.h", "gnms_prof.h", "iou_tile.h", "iou_grad.h", "cuboid_corners.h", "bev_clip.h", "iou3d_pair.h", "iou3d_tile.h", "iou3d_sym.h", "gnms_device.h", "sort_bins.h", "nms_sort_kernels.h", "nms_scan_kernels.h", "nms_kernels.h", "nms_one_launch.h", "nms_backward_kernels.h", "nms_solve_kernels.h",
-           os.path.join("..", "..", "include", "groomed_nms_hip.h")]
+# Longest compile first (LABNOTES R15): the jobs start in this order, so the NMS layer's units -- 15 to 30 s each, everything else under 6 s -- go
+# ahead of the small sources and a clean build takes about as long as the slowest of them.
+SOURCES = ["nms_layer.hip", "nms_tail_write_records.hip", "nms_tail_write_boxes.hip", "nms_tail_boxes.hip", "nms_tail_matrix.hip", "nms_tail_records.hip",
+           "soft_sort.hip", "aploss.hip", "iou_kernels.hip", "classic_nms.hip", "nms_profile.hip", "nms_others.hip", "proposals.hip", "host_mailbox.hip", "iou3d_exact.hip", "targets.hip", "detect3d.hip", "kitti_eval.hip", "kitti_rows.hip", "sampling.hip", "regression.hip", "after_nms.hip", "heads.hip", "loss.hip", "bbox_stats.hip", "preprocess.hip", "optim.hip", "iou_backward.hip"]
 # -ffp-contract=off: products and sums round separately, like the reference's torch CPU kernels
 # (lib/core.py:499-508) -- this is what makes the overlap matrices bit-identical.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
@@ -31,22 +32,41 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _depfile_deps(path):
+    """The prerequisites in a make-style dependency file (hipcc -MD -MF), or None where it cannot be read."""
+    try:
+        text = open(path).read()
+    except OSError:
+        return None
+    return text.replace("\\\n", " ").partition(":")[2].split()
+
+
+def _jobs():
+    """MAX_JOBS if set, else 8; never above 16."""
+    try:
+        n = int(os.environ.get("MAX_JOBS", ""))
+    except ValueError:
+        n = 8
+    return max(1, min(n, 16))
+
+
 def build(force=False, verbose=False):
-    # objects compiled with other flags (GNMS_EXTRA_FLAGS experiments) are stale whatever their timestamps say
+    # objects compiled with other flags (GNMS_EXTRA_FLAGS experiments) are stale whatever else: the stamp is rewritten when the flags change
+    # and every object depends on it
     stamp = os.path.join(CSRC, ".build_flags")
     flags = " ".join(FLAGS)
     if not os.path.exists(stamp) or open(stamp).read() != flags:
-        force = True
-    with open(stamp, "w") as f:
-        f.write(flags)
-    deps = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)]
+        with open(stamp, "w") as f:
+            f.write(flags)
     objs, jobs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, src.replace(".hip", ".o"))
+        d = o[:-2] + ".d"                                    # what the compiler read for this object (-MD): the headers it really includes
         objs.append(o)
-        if force or _stale(o, [s] + deps):
-            jobs.append([hipcc()] + FLAGS + ["-c", s, "-o", o])
+        deps = _depfile_deps(d)
+        if force or deps is None or not all(os.path.exists(p) for p in deps) or _stale(o, [s, stamp, os.path.abspath(__file__)] + deps):
+            jobs.append([hipcc()] + FLAGS + ["-MD", "-MF", d, "-c", s, "-o", o])
     if jobs:
         def run(cmd):
             if verbose:
@@ -56,7 +76,7 @@ def build(force=False, verbose=False):
                 raise RuntimeError("hipcc failed:\n%s\n%s" % (" ".join(cmd), r.stderr[-6000:]))
             if verbose and r.stderr.strip():
                 print(r.stderr[-3000:])
-        with ThreadPoolExecutor(max_workers=4) as ex:
+        with ThreadPoolExecutor(max_workers=_jobs()) as ex:                # (jobs start in SOURCES' order: longest first)
             list(ex.map(run, jobs))
     if jobs or force or _stale(OUT, objs):
         cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs

@@ -14,7 +14,7 @@
 #include <mutex>
 #include <vector>
 #include <string.h>
-#include "nms_scan_kernels.h"
+#include "nms_leaders_kernel.h"
 
 namespace {
 

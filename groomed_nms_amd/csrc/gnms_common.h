@@ -81,6 +81,15 @@ struct gnms_poll_backoff {
     bool wait();
 };
 
+namespace gnms {
+// Where the kernels that need single overlap entries take them from.  The template parameter is an int so that the existing
+// <false> / <true> instantiations keep meaning "matrix" / "2D boxes".  (Here and not in gnms_device.h: the host header of the layer's
+// units, nms_layer.h, names them in its launchers' declarations.)
+constexpr int kFromMatrix = 0;     // src = the N x N matrix of the image, leading dimension ld
+constexpr int kFromBoxes = 1;      // src = the image's boxes [N][4]: lib/core.py iou recomputed (pair_iou, the arithmetic of iou2d_tile)
+constexpr int kFromRecords = 2;    // src = the image's corner-AABB records [N][12]: 0.5 * (1 + GIoU3D) recomputed (iou3d_pair.h)
+}  // namespace gnms
+
 static inline int gnms_div_up(int a, int b) { return (a + b - 1) / b; }
 static inline size_t gnms_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 

@@ -209,13 +209,7 @@ __device__ __forceinline__ float pair_iou(const float4 a, const float4 b) {
     return inter / ((area_a + area_b) - inter);
 }
 
-// Where the kernels that need single overlap entries take them from.  The template parameter is an int so that the existing
-// <false> / <true> instantiations keep meaning "matrix" / "2D boxes".
-constexpr int kFromMatrix = 0;     // src = the N x N matrix of the image, leading dimension ld
-constexpr int kFromBoxes = 1;      // src = the image's boxes [N][4]: lib/core.py iou recomputed (pair_iou, the arithmetic of iou2d_tile)
-constexpr int kFromRecords = 2;    // src = the image's corner-AABB records [N][12]: 0.5 * (1 + GIoU3D) recomputed (iou3d_pair.h)
-
-// element [ca][cb] (input indices)
+// element [ca][cb] (input indices) of the overlaps' source SRC (kFromMatrix / kFromBoxes / kFromRecords: gnms_common.h)
 // thr: the layer's nms_threshold (records only: entries inside the guard band around it take the reference's exact order, iou3d_pair.h)
 template <int SRC>
 __device__ __forceinline__ float overlap_at(const float* __restrict__ src, long ld, int ca, int cb, float thr) {

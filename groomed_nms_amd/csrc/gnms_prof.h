@@ -1,7 +1,7 @@
 // gnms_prof.h -- per-launch timing of the library's HBM-bound launches (gnms_profile_events / gnms_profile_collect).
 // Armed, such a launch goes through hipExtLaunchKernel with a start and a stop event: the events then carry the dispatch's own
 // begin / end timestamps -- the interval a kernel trace (rocprofv3 --kernel-trace) reports for it -- without any marker packet in
-// the stream.  Disarmed (the default) a launch costs one relaxed atomic load more than a plain <<<>>>.  State: nms_layer.hip.
+// the stream.  Disarmed (the default) a launch costs one relaxed atomic load more than a plain <<<>>>.  State: nms_profile.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

@@ -1,5 +1,5 @@
 // iou3d_tile.h -- the wave tile of the 3D NMS-overlap matrix 0.5 * (1 + GIoU3D), shared by iou3d_nms_fast_kernel (iou_kernels.hip)
-// and the launch that carries the per-image chain beside the write (nms_layer.hip).  Reference: lib/core.py:305-421 (generalized),
+// and the launch that carries the per-image chain beside the write (tail_write_kernel, nms_writers.h).  Reference: lib/core.py:305-421 (generalized),
 // lib/loss/rpn_3d.py:781; arithmetic and guard band: iou3d_pair.h.
 #pragma once
 #include "iou3d_pair.h"

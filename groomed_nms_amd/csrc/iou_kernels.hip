@@ -309,7 +309,7 @@ __global__ __launch_bounds__(NW * 64) void iou3d_sym_kernel(const float* __restr
 // The same writer as PERSISTENT workgroups (one 16-wave workgroup per CU): workgroup w takes the macro tiles w, w + G, w + 2 G, ... of
 // the batch (image-major, row-major over each triangle) -- together the G workgroups advance one frontier through the matrices -- and
 // alternates between two LDS tiles, so that one barrier per tile suffices and the mirrored stores of a tile overlap the arithmetic of
-// the next (the layer's writers_sym_persistent, nms_layer.hip, with a static round robin instead of claims: no counter to reset).
+// the next (the layer's writers_sym_persistent, nms_writers.h, with a static round robin instead of claims: no counter to reset).
 template <bool NT>
 __global__ __launch_bounds__(1024) void iou3d_sym_persistent_kernel(const float* __restrict__ rec, int N, int nimg, float* __restrict__ out, long ld,
                                                                     float thr) {

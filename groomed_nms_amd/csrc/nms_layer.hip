@@ -1,5 +1,7 @@
 // nms_layer.hip -- host side of the GrooMeD-NMS C ABI: argument checks, workspace carving, launches.
-// Kernels: nms_kernels.h (forward), nms_backward_kernels.h, nms_solve_kernels.h.
+// Kernels: nms_kernels.h / nms_layer_kernels.h (forward), nms_backward_kernels.h, nms_solve_kernels.h, nms_one_launch.h.
+// Not here: tail_kernel and tail_write_kernel with their launchers (the nms_tail_*.hip / nms_tail_write_*.hip units) and the
+// gnms_profile_* entries (nms_profile.hip); nms_layer.h is what these units share, and its definitions are in this file.
 #include <stdarg.h>
 #include <string.h>
 
@@ -13,8 +15,11 @@
 #include "iou_tile.h"
 #include "iou3d_tile.h"
 #include "iou3d_sym.h"
+#include "nms_layer_kernels.h"
 #include "nms_solve_kernels.h"
 #include "nms_one_launch.h"
+#include "nms_writers.h"
+#include "nms_layer.h"
 
 // defined in iou_kernels.hip
 bool gnms_internal_overlap3d_sym_ok(int N, int64_t ld, const float* out);
@@ -36,128 +41,6 @@ void gnms_set_error(const char* fmt, ...) {
 
 extern "C" const char* gnms_last_error(void) { return g_err; }
 
-// ------------------------------------------------------------------------------------------------
-// profiling: event pairs around the HBM-bound launches (bench.py's roofline is computed from these)
-// ------------------------------------------------------------------------------------------------
-namespace {
-struct ProfPair { int dev; hipEvent_t start, stop; };
-struct ProfState {
-    std::atomic<bool> armed{false};
-    std::mutex mu;
-    std::map<int, std::vector<hipEvent_t>> pool;                   // recycled events, per device (an event belongs to the device it was created on)
-    std::vector<ProfPair> pairs[kProfSlots];
-    hipEvent_t take(int dev) {
-        std::vector<hipEvent_t>& p = pool[dev];
-        if (!p.empty()) { hipEvent_t e = p.back(); p.pop_back(); return e; }
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        return e;
-    }
-};
-ProfState& prof() { static ProfState P; return P; }
-}  // namespace
-
-bool gnms_prof_armed() { return prof().armed.load(std::memory_order_relaxed); }
-bool gnms_prof_pair(int slot, hipEvent_t* start, hipEvent_t* stop) {
-    ProfState& P = prof();
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    std::lock_guard<std::mutex> lock(P.mu);
-    hipEvent_t a = P.take(dev), b = P.take(dev);
-    if (!a || !b) { if (a) P.pool[dev].push_back(a); if (b) P.pool[dev].push_back(b); return false; }
-    P.pairs[slot].push_back(ProfPair{dev, a, b});
-    *start = a;
-    *stop = b;
-    return true;
-}
-
-extern "C" int gnms_profile_events(int enable) {
-    prof().armed.store(enable != 0, std::memory_order_relaxed);
-    return GNMS_OK;
-}
-
-extern "C" int gnms_profile_collect(int slot, double* ms_sum, int* launches) {
-    GNMS_CHECK_ARG(slot >= 0 && slot < kProfSlots && ms_sum && launches, "gnms_profile_collect: bad argument");
-    ProfState& P = prof();
-    std::lock_guard<std::mutex> lock(P.mu);
-    double sum = 0.0;
-    int n = 0;
-    hipError_t first_err = hipSuccess;
-    // every pair leaves the list and goes back to its device's pool whatever happens: an error on one pair is reported after the
-    // walk, it never strands the others (or leaves recycled events behind in the list)
-    for (const ProfPair& pr : P.pairs[slot]) {
-        float ms = 0.0f;
-        hipError_t e = hipEventSynchronize(pr.stop);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, pr.start, pr.stop);
-        if (e == hipSuccess) { sum += ms; ++n; }
-        else if (first_err == hipSuccess) first_err = e;
-        P.pool[pr.dev].push_back(pr.start);
-        P.pool[pr.dev].push_back(pr.stop);
-    }
-    P.pairs[slot].clear();
-    *ms_sum = sum;
-    *launches = n;
-    if (first_err != hipSuccess) {
-        gnms_set_error("gnms_profile_collect: %s", hipGetErrorString(first_err));
-        return GNMS_ERR_HIP;
-    }
-    return GNMS_OK;
-}
-
-namespace {
-// plain streams: what the HBM delivers to a kernel that does nothing else (the achievable ceiling the roofline is quoted beside)
-__global__ __launch_bounds__(512) void prof_fill_kernel(float4* __restrict__ dst, size_t n4, float v) {
-    const float4 x = make_float4(v, v, v, v);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        float* p = reinterpret_cast<float*>(dst + i);
-        __builtin_nontemporal_store(x.x, p); __builtin_nontemporal_store(x.y, p + 1);
-        __builtin_nontemporal_store(x.z, p + 2); __builtin_nontemporal_store(x.w, p + 3);
-    }
-}
-__global__ __launch_bounds__(512) void prof_read_kernel(const float4* __restrict__ src, size_t n4, float* __restrict__ sink) {
-    float acc = 0.0f;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        const float* p = reinterpret_cast<const float*>(src + i);
-        acc += __builtin_nontemporal_load(p) + __builtin_nontemporal_load(p + 1) + __builtin_nontemporal_load(p + 2) + __builtin_nontemporal_load(p + 3);
-    }
-    if (acc == 123456.789f) *sink = acc;                          // never true for the data it is run on; keeps the loads alive
-}
-// the same bytes in the geometry of the matrix writers: a wave stores ROWS rows x 1 KiB (rows `ld` floats apart), 16 waves side by side,
-// one workgroup per CU walking the row bands -- no loads, no arithmetic
-template <int ROWS, bool NT>
-__global__ __launch_bounds__(1024) void prof_fill_tiles_kernel(float* __restrict__ dst, int N, long ld, long bands, float v, int order) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ncc = (N + 255) >> 8;
-    const int ncg = (ncc + 15) >> 4;                              // column groups of 16 wave tiles (4096 columns)
-    const long units = bands * ncg;
-    const long bands_img = N / ROWS;
-    const long per = (units + gridDim.x - 1) / gridDim.x;
-    for (long u = order == 2 ? blockIdx.x * per : blockIdx.x; u < (order == 2 ? min(units, (blockIdx.x + 1) * per) : units); u += order == 2 ? 1 : gridDim.x) {
-        long band;
-        int g;
-        if (order == 0) { band = u / ncg; g = (int)(u - band * ncg); }           // row band major: a band's column groups side by side
-        else {                                                                    // (image, column group) major: bands of one group in a row
-            const long pair = u / bands_img, bi = u - pair * bands_img;
-            const long img = pair / ncg;
-            g = (int)(pair - img * ncg);
-            band = img * bands_img + bi;
-        }
-        const int col = (g * 16 + wave) * 256 + 4 * lane;
-        if (col + 3 >= N) continue;
-        float* p = dst + band * ROWS * ld + col;
-#pragma unroll 16
-        for (int r = 0; r < ROWS; ++r) {
-            if (NT) {
-                __builtin_nontemporal_store(v, p); __builtin_nontemporal_store(v, p + 1);
-                __builtin_nontemporal_store(v, p + 2); __builtin_nontemporal_store(v, p + 3);
-            } else {
-                *reinterpret_cast<float4*>(p) = make_float4(v, v, v, v);
-            }
-            p += ld;
-        }
-    }
-}
-}  // namespace
 // compute units of the current device, cached per device (declared in gnms_common.h)
 int gnms_device_cu_count() {
     static std::mutex mu;
@@ -171,107 +54,6 @@ int gnms_device_cu_count() {
         c = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
     }
     return c;
-}
-extern "C" int gnms_profile_fill_tiles(float* dst, int B, int N, int64_t ld, int rows, int nontemporal, void* stream) {
-    GNMS_CHECK_ARG(dst && B > 0 && N > 0 && ld >= N && ld % 4 == 0 && (uintptr_t)dst % 16 == 0,
-                   "gnms_profile_fill_tiles: dst 16-byte aligned, ld >= N a multiple of 4");
-    GNMS_CHECK_ARG((rows == 4 || rows == 8 || rows == 16 || rows == 32 || rows == 64) && N % rows == 0,
-                   "gnms_profile_fill_tiles: rows per wave tile must be 4, 8, 16, 32 or 64 and divide N (rows=%d N=%d)", rows, N);
-    const int order = 0;                                           // row band major (the other orders of round 2 measured slower: LABNOTES.md)
-    const dim3 grid((unsigned)gnms_device_cu_count());
-    hipStream_t st = (hipStream_t)stream;
-    const long bands = (long)B * N / rows;
-#define GNMS_FILL_TILES(R)                                                                                                                  \
-    do {                                                                                                                                    \
-        if (nontemporal) gnms_launch_prof(kProfPlainStream, prof_fill_tiles_kernel<R, true>, grid, dim3(1024), 0, st, dst, N, (long)ld, bands, 0.5f, order);   \
-        else gnms_launch_prof(kProfPlainStream, prof_fill_tiles_kernel<R, false>, grid, dim3(1024), 0, st, dst, N, (long)ld, bands, 0.5f, order);            \
-    } while (0)
-    switch (rows) {
-        case 4: GNMS_FILL_TILES(4); break;
-        case 8: GNMS_FILL_TILES(8); break;
-        case 16: GNMS_FILL_TILES(16); break;
-        case 32: GNMS_FILL_TILES(32); break;
-        default: GNMS_FILL_TILES(64); break;
-    }
-#undef GNMS_FILL_TILES
-    GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
-}
-namespace {
-// The store pattern of a SYMMETRIC matrix writer, with no arithmetic: upper-triangular T x T macro tiles, each written once where it
-// is and once mirrored (rows <-> columns), row runs of T floats.  CPL floats per lane and store instruction: T / CPL lanes cover a row
-// run, 64 / (T / CPL) row runs per instruction.  persist: one workgroup per CU walks a contiguous range of tiles (row-major over the
-// upper triangle: a strip I, J = I .. end), else one workgroup per tile.
-template <int T, int CPL, bool NT>
-__global__ __launch_bounds__(1024) void prof_fill_sym_kernel(float* __restrict__ dst, int N, long ld, int nimg, int persist, float v) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-    constexpr int LPR = T / CPL, RPI = 64 / LPR;
-    const int RW = T / waves;
-    const int nt = N / T;
-    const long per_img = (long)nt * (nt + 1) / 2, total = per_img * nimg;
-    long t0 = blockIdx.x, t1 = blockIdx.x + 1;
-    if (persist) { t0 = total * blockIdx.x / gridDim.x; t1 = total * (blockIdx.x + 1) / gridDim.x; }
-    const long step = persist == 2 ? gridDim.x : 1;                  // persist 2: round robin (one compact write frontier), else contiguous strips
-    if (persist == 2) { t0 = blockIdx.x; t1 = total; }
-    for (long t = t0; t < t1 && t < total; t += step) {
-        const int img = (int)(t / per_img);
-        long r = t - (long)img * per_img;
-        int I = 0;
-        while (r >= nt - I) { r -= nt - I; ++I; }                      // (a benchmark: the linear walk is a few dozen trips)
-        const int J = I + (int)r;
-        float* base = dst + (size_t)img * N * ld;
-        auto put = [&](int R0, int C0) {
-            for (int rr = 0; rr < RW; rr += RPI) {
-                float* p = base + (size_t)(R0 + wave * RW + rr + lane / LPR) * ld + C0 + (lane % LPR) * CPL;
-                if (NT) {
-#pragma unroll
-                    for (int j = 0; j < CPL; ++j) __builtin_nontemporal_store(v, p + j);
-                } else if (CPL == 4) {
-                    *reinterpret_cast<float4*>(p) = make_float4(v, v, v, v);
-                } else {
-                    *reinterpret_cast<float2*>(p) = make_float2(v, v);
-                }
-            }
-        };
-        put(I * T, J * T);
-        if (I != J) put(J * T, I * T);
-    }
-}
-}  // namespace
-extern "C" int gnms_profile_fill_sym(float* dst, int B, int N, int64_t ld, int tile, int cols_per_lane, int nontemporal, int persist, void* stream) {
-    GNMS_CHECK_ARG(dst && B > 0 && N > 0 && ld >= N && ld % 4 == 0 && (uintptr_t)dst % 16 == 0, "gnms_profile_fill_sym: dst 16-byte aligned, ld >= N a multiple of 4");
-    GNMS_CHECK_ARG((tile == 128 || tile == 256) && N % tile == 0 && (cols_per_lane == 2 || cols_per_lane == 4) && tile / cols_per_lane <= 64,
-                   "gnms_profile_fill_sym: tile 128 or 256 dividing N, 2 or 4 columns per lane");
-    hipStream_t st = (hipStream_t)stream;
-    const int nt = N / tile;
-    const long total = (long)nt * (nt + 1) / 2 * B;
-    const dim3 grid((unsigned)(persist ? gnms_device_cu_count() * (tile == 128 ? 2 : 1) : total));
-    const dim3 block(tile == 128 ? 512 : 1024);
-#define GNMS_FILL_SYM(TT, CC)                                                                                                              \
-    do {                                                                                                                                   \
-        if (nontemporal) gnms_launch_prof(kProfPlainStream, prof_fill_sym_kernel<TT, CC, true>, grid, block, 0, st, dst, N, (long)ld, B, persist, 0.5f);   \
-        else gnms_launch_prof(kProfPlainStream, prof_fill_sym_kernel<TT, CC, false>, grid, block, 0, st, dst, N, (long)ld, B, persist, 0.5f);            \
-    } while (0)
-    if (tile == 128 && cols_per_lane == 2) GNMS_FILL_SYM(128, 2);
-    else if (tile == 128) GNMS_FILL_SYM(128, 4);
-    else GNMS_FILL_SYM(256, 4);
-#undef GNMS_FILL_SYM
-    GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
-}
-extern "C" int gnms_profile_fill(float* dst, size_t count, void* stream) {
-    GNMS_CHECK_ARG(dst && count % 4 == 0 && (uintptr_t)dst % 16 == 0, "gnms_profile_fill: dst must be 16-byte aligned, count a multiple of 4");
-    if (count == 0) return GNMS_OK;
-    gnms_launch_prof(kProfPlainStream, prof_fill_kernel, dim3(256 * 16), dim3(512), 0, (hipStream_t)stream, reinterpret_cast<float4*>(dst), count / 4, 0.5f);
-    GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
-}
-extern "C" int gnms_profile_read(const float* src, size_t count, float* sink, void* stream) {
-    GNMS_CHECK_ARG(src && sink && count % 4 == 0 && (uintptr_t)src % 16 == 0, "gnms_profile_read: src must be 16-byte aligned, count a multiple of 4");
-    if (count == 0) return GNMS_OK;
-    gnms_launch_prof(kProfPlainStream, prof_read_kernel, dim3(256 * 16), dim3(512), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(src), count / 4, sink);
-    GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
 }
 extern "C" int gnms_abi_version(void) { return GNMS_ABI_VERSION; }
 
@@ -304,9 +86,10 @@ int gnms_allow_lds_raw(const void* kernel, size_t bytes) {
     return GNMS_OK;
 }
 
-namespace {
-
-using namespace gnms;
+// ------------------------------------------------------------------------------------------------
+// what the layer's units share (nms_layer.h): the one definition of each
+// ------------------------------------------------------------------------------------------------
+namespace gnms {
 
 int next_pow2(int n) {
     int p = 64;               // block_sort works on >= 64 keys (one wave)
@@ -314,21 +97,7 @@ int next_pow2(int n) {
     return p;
 }
 
-// block_sort<E>: P = threads * E.  P <= 1024 -> E = 1; above, 1024 threads and E = P / 1024 (N <= 16384 -> E <= 16).
-#define GNMS_DISPATCH_SORT(P2, ...)                               \
-    do {                                                          \
-        const int e__ = (P2) <= 1024 ? 1 : (P2) / 1024;           \
-        if (e__ == 1) { constexpr int E = 1; __VA_ARGS__; }              \
-        else if (e__ == 2) { constexpr int E = 2; __VA_ARGS__; }         \
-        else if (e__ == 4) { constexpr int E = 4; __VA_ARGS__; }         \
-        else if (e__ == 8) { constexpr int E = 8; __VA_ARGS__; }         \
-        else { constexpr int E = 16; __VA_ARGS__; }                      \
-    } while (0)
-
 size_t leaders_lds_bytes(int N) { return leaders_lds_size((N + 63) / 64); }
-
-template <typename K>
-int allow_lds(K kernel, size_t bytes) { return gnms_allow_lds_raw(reinterpret_cast<const void*>(kernel), bytes); }
 
 int check_common(const char* fn, int B, int N, int64_t ld, const gnms_params* P, const void* ws, size_t ws_bytes) {
     GNMS_CHECK_ARG(P != nullptr, "%s: params is NULL", fn);
@@ -380,33 +149,14 @@ bool matrix_sym_detection(int N) {
     return forced >= 0 ? forced != 0 : N >= 256;
 }
 
-// What every launcher of the layer is handed: the sizes, the workspace, the stream and the outputs of one call.
-struct LayerCall {
-    int B, N;
-    const int32_t* counts;
-    gnms_params P;
-    gnms_ws_layout L;
-    char* ws;
-    hipStream_t st;
-    int P2;                                                       // keys of the block sorts: next_pow2(N)
-    float* prob;
-    int64_t *order, *valid, *invalid;
-    int32_t *nvalid, *ninvalid;
-    size_t sort_lds() const { return (size_t)P2 * 8; }
-    int sort_threads() const { return P2 <= 1024 ? P2 : 1024; }
-};
-LayerCall make_call(int B, int N, const int32_t* counts, const gnms_params& P, void* workspace, void* stream, float* prob = nullptr,
-                    int64_t* order = nullptr, int64_t* valid = nullptr, int64_t* invalid = nullptr, int32_t* nvalid = nullptr,
-                    int32_t* ninvalid = nullptr) {
+LayerCall make_call(int B, int N, const int32_t* counts, const gnms_params& P, void* workspace, void* stream, float* prob, int64_t* order,
+                    int64_t* valid, int64_t* invalid, int32_t* nvalid, int32_t* ninvalid) {
     return LayerCall{B, N, counts, P, gnms_make_layout(N), (char*)workspace, (hipStream_t)stream, next_pow2(N), prob, order, valid, invalid, nvalid, ninvalid};
 }
-// The prologue of an entry: the checks, then the call.  kCallEmpty (> 0: not an error code): nothing to launch -- B == 0, or N == 0, where the
-// counts the call has are zeroed.  without_matrix: an entry that has the boxes only, the grouped hard-sorted modes; ptrs_ok: the entry's own
-// pointers are all there (asked only of a call that is not empty; null_msg says which entry).
-constexpr int kCallEmpty = 1;
+// the prologue of an entry (nms_layer.h)
 int begin_call(const char* fn, LayerCall* c, int B, int N, int64_t ld, const int32_t* counts, const gnms_params* params, void* workspace,
-               size_t workspace_bytes, void* stream, bool without_matrix, bool ptrs_ok, const char* null_msg, float* prob = nullptr,
-               int64_t* order = nullptr, int64_t* valid = nullptr, int64_t* invalid = nullptr, int32_t* nvalid = nullptr, int32_t* ninvalid = nullptr) {
+               size_t workspace_bytes, void* stream, bool without_matrix, bool ptrs_ok, const char* null_msg, float* prob, int64_t* order,
+               int64_t* valid, int64_t* invalid, int32_t* nvalid, int32_t* ninvalid) {
     int rc = check_common(fn, B, N, ld, params, workspace, workspace_bytes);
     if (rc) return rc;
     if (without_matrix && (!params->group_boxes || params->presorted)) {
@@ -424,18 +174,26 @@ int begin_call(const char* fn, LayerCall* c, int B, int N, int64_t ld, const int
     *c = make_call(B, N, counts, *params, workspace, stream, prob, order, valid, invalid, nvalid, ninvalid);
     return GNMS_OK;
 }
-// the entries return through this: an empty call is a success
-#define GNMS_BEGIN_CALL(...)                                      \
-    do {                                                          \
-        const int rc__ = begin_call(__VA_ARGS__);                 \
-        if (rc__) return rc__ == kCallEmpty ? GNMS_OK : rc__;     \
-    } while (0)
 
-// the direction of the per-group solves (solve_groups_kernel's BWD)
-constexpr bool kForward = false, kBackward = true;
+// K3..K6 in one launch (masked groups): the fast tail (nms_kernels.h) is on unless GNMS_FAST_TAIL=0 (developer switch: the K5-proper path
+// stays reachable for A/B runs and tests)
+bool fast_tail_enabled() { static const bool on = env_switch("GNMS_FAST_TAIL", 1) != 0; return on; }
+
+// dynamic LDS of the chain in tail_kernel / tail_write_kernel; P2: the launch's key count (>= 1024: the fused kernels always run 1024 threads)
+size_t tail_lds_bytes(int N, int P2, int fast) {
+    // (the fused K5 -> K6 hand-off, E <= 4, parks order[] and a copy of r2 behind the key region: 16 bytes per key)
+    const size_t llds = leaders_lds_bytes(N), glds = (size_t)P2 * (P2 <= 4096 ? 16 : 8);
+    size_t lds = llds > glds ? llds : glds;
+    if (fast && lds < fast_tail_lds_size(N, P2)) lds = fast_tail_lds_size(N, P2);
+    return lds;
+}
+
+}  // namespace gnms
+
+using namespace gnms;
 
 // full: 0 = only the words a leader scan reads; 1 = whole rows + wsym_check_kernel behind; 2 = whole rows, the check rides in the tail launch
-int launch_bitmask(const LayerCall& c, const float* iou, int64_t ld, int full = 0) {
+int gnms_internal_launch_bitmask(const LayerCall& c, const float* iou, int64_t ld, int full) {
     const int B = c.B, N = c.N;
     const gnms_ws_layout& L = c.L;
     // (measured at B = 8, N = 4096, three interleaved repetitions: 16 waves 91.6-91.8 us = 0.733 of the HBM peak, 8 waves 95.2-95.7 us;
@@ -460,6 +218,11 @@ int launch_bitmask(const LayerCall& c, const float* iou, int64_t ld, int full = 
     }
     return GNMS_OK;
 }
+
+namespace {
+
+// the direction of the per-group solves (solve_groups_kernel's BWD)
+constexpr bool kForward = false, kBackward = true;
 
 // ------------------------------------------------------------------------------------------------
 // K3..K6 as launches of their own, one launcher per block; src / ld: the overlaps' source (SRC: kFromMatrix, kFromBoxes, kFromRecords)
@@ -531,214 +294,6 @@ extern "C" size_t gnms_workspace_bytes(int B, int N, const gnms_params* params) 
 }
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------
-// The matrix write as a ROLE inside the launch of the per-image chain (masked from-boxes layer, gnms_forward_with_iou2d).
-// Nothing in that layer reads the matrix, so the write is independent of the chain sorts -> threshold bits -> K3..K6.  As launches of
-// their own the chain K3..K6 (one workgroup per image: 8 of 256 CUs at B = 8) ran strictly behind the write; as two streams the fork
-// and join cost more than the overlap bought (LABNOTES.md 3.2d).  tail_write_kernel is both in ONE launch: the first B x nsb workgroups ARE
-// the chain (the device functions of tail_kernel), the others write the matrix.  The launch asks for the chain's LDS (> 80 KiB), so a
-// CU holds ONE workgroup: the chain workgroups are dispatched first and have a CU each to themselves (beside the write they run
-// within 10 % of their stand-alone time; sharing a CU with streaming waves they ran 1.5-3x slower), the other CUs stream the matrix;
-// when a chain workgroup retires, a writer still waiting in the grid takes its CU.
-// A chunk = 16 wave tiles of tile_rows x 256 entries (tile_rows full rows of one image at N = 4096), written by the 16 waves of a
-// workgroup with iou2d_tile -- the tile code of gnms_iou2d, so the matrix is the same bit for bit.
-// Measured and dropped: slices of the write ALSO inside the sort launches and the bit-matrix launch (7 % / 5 % / 10-20 % of the rows,
-// behind those kernels' own workgroups in the grid).  The sort and bit-matrix workgroups then share their CUs with streaming waves
-// and slow down by more than the slices save: sort runs 7.8 -> 15.6 us, merges 5.9 -> 15.0, bit matrix 24 -> 46, chain + rest of the
-// write 114 -> 98 (B = 8, N = 4096: 0.172 -> 0.173-0.184 ms per step for every split tried).
-// ------------------------------------------------------------------------------------------------
-__host__ __device__ inline int write_chunk_count(int N, int nimg, int tile_rows, int row0, int row_end) {
-    if (row_end <= row0) return 0;
-    const long tiles = (long)nimg * ((N + gnms_iou::kWaveCols - 1) / gnms_iou::kWaveCols) * ((row_end - row0 + tile_rows - 1) / tile_rows);
-    return (int)((tiles + 15) >> 4);
-}
-
-// what the writers compute: SRC = kFromBoxes: `in` = boxes [B][N][4], lib/core.py iou (iou2d_tile);
-// SRC = kFromRecords: `in` = corner-AABB records [B][N][12], 0.5 * (1 + GIoU3D) with the guard band around `thr` (nms_overlap3d_tile)
-template <bool VEC, int SRC>
-__device__ __forceinline__ void write_chunk(const float* __restrict__ in, int N, float* __restrict__ out, long ld, int nimg, int tile_rows,
-                                            int row0, int row_end, float thr, int chunk) {
-    using namespace gnms_iou;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ncc = (N + kWaveCols - 1) / kWaveCols;
-    const int nrt = (row_end - row0 + tile_rows - 1) / tile_rows;
-    const int per_img = ncc * nrt;
-    const int t = chunk * 16 + wave;                               // tiles numbered image-major, column chunk fastest
-    if (t >= per_img * nimg) return;
-    const int img = t / per_img;
-    const int r = t - img * per_img;
-    const int rt = r / ncc, cc = r - rt * ncc;
-    if (SRC == kFromRecords)
-        gnms_iou3d::nms_overlap3d_tile<VEC>(in, in, N, N, out, ld, img, row0 + rt * tile_rows, cc * kWaveCols, lane, tile_rows, row_end, thr);
-    else
-        iou2d_tile<VEC>(in, in, N, N, out, ld, img, row0 + rt * tile_rows, cc * kWaveCols, lane, tile_rows, row_end);
-}
-
-// PERSISTENT writers: one workgroup stays on its CU and claims chunk after chunk from `counter` (zeroed by the sort kernels of this
-// call), one claim ahead so that the atomic's round trip hides behind the chunk in progress.  Claims are the ONLY cross-workgroup
-// traffic of the launch: anything that needs a release/acquire fence between workgroups (the whole chain sorts -> bits -> K3..K6 as
-// tasks of one persistent launch was the plan) is out of the question beside the write stream -- one __threadfence() per chunk
-// (buffer_wbl2 + buffer_inv at agent scope) took this launch from 0.115 to 1.13 ms.  (Ordinary workgroups of one chunk each
-// leave the CU empty between a workgroup's last wave and the next workgroup's start, and with one workgroup per CU nothing covers
-// that gap: 116 against 107 us.  One claim per WAVE tile serialises on the counter: 16384 device-scope atomics on one address took
-// 430 us.)
-template <bool VEC, int SRC>
-__device__ __forceinline__ void writers_persistent(const float* __restrict__ in, int N, float* __restrict__ out, long ld, int nimg,
-                                                   int tile_rows, int row0, int row_end, float thr, int* counter) {
-    __shared__ int s_next[2];
-    const int nchunks = write_chunk_count(N, nimg, tile_rows, row0, row_end);
-    if (threadIdx.x == 0) s_next[0] = atomicAdd(counter, 1);
-    __syncthreads();
-    int cur = s_next[0], ph = 0;
-    while (cur < nchunks) {
-        int nx = 0;
-        if (threadIdx.x == 0) nx = atomicAdd(counter, 1);          // the claim after this one, in flight during the chunk
-        write_chunk<VEC, SRC>(in, N, out, ld, nimg, tile_rows, row0, row_end, thr, cur);
-        if (threadIdx.x == 0) s_next[ph ^ 1] = nx;
-        __syncthreads();
-        ph ^= 1;
-        cur = s_next[ph];
-    }
-}
-
-// STAGED writers (2D, N <= 4096): what keeps the persistent writers above from the rate of a plain store stream is vmcnt.  On gfx9
-// loads, stores and returning atomics retire through ONE in-order counter, so the wave that waits for its next tile's boxes (5 loads)
-// first waits for the 16 stores of the tile before, and thread 0, waiting for its claim, drains wave 0's stores while 15 waves sit at
-// the barrier -- at 16 waves per CU nothing covers those gaps (tail_write_kernel 0.115 ms where gnms_iou2d's many small workgroups
-// take 0.100).  Here the steady state has no vector load at all:
-//   * the image's boxes are staged in LDS once per (workgroup, image) -- the chain's dynamic LDS, unused by writer workgroups -- and a
-//     tile reads its column and row boxes from there (lgkmcnt);
-//   * every image has its own claim counter (misc[5] of its workspace, zeroed by its sort) and a workgroup starts on image
-//     (index mod B), moving on when that image is exhausted: 1-2 stagings per workgroup instead of B;
-//   * the claim for the unit after next is issued BEFORE the tile's stores and consumed after them, the rows unrolled so that the
-//     compiler counts the stores behind it and waits with vmcnt(8), not vmcnt(0).  (The atomic's address is made lane-dependent on
-//     purpose: with a wave-uniform address the compiler's atomic optimizer wraps it in a readfirstlane that needs the result at once.)
-// A unit = 16 wave tiles of 8 rows x 256 columns, numbered row band major inside an image.  (Rows per tile, B = 8: 16 -> 8 took the
-// launch at N = 4096 from 102.5 to 93.0 us and the large-image launch at N = 16384 from 1.57 to 1.45 ms -- twice as many, shorter units
-// even out what 2048 units on 248 workgroups leave uneven; 4 rows lose again, 111 us / 1.77 ms.)
-constexpr int kStagedRows = 8;
-
-// claim0 / claim_stride: image i's claim counter is claim0[i * claim_stride] (the layer: misc[5] of the image's workspace; gnms_iou2d:
-// a zeroed array of its own); first_wg: blockIdx.x of the first writer workgroup of the launch
-template <bool VEC>
-__device__ __forceinline__ void writers_staged_2d(const float* __restrict__ boxes, int N, float* __restrict__ out, long ld, int nimg, int* claim0,
-                                                  size_t claim_stride, const int first_wg) {
-    using namespace gnms_iou;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4* sbox = reinterpret_cast<float4*>(smem);                  // [N] boxes of the staged image
-    __shared__ int s_claim[2];                                       // (image << 16 | unit) or -1
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ncc = (N + kWaveCols - 1) / kWaveCols;
-    const int nrt = (N + kStagedRows - 1) / kStagedRows;
-    const int units = (ncc * nrt + 15) >> 4;
-    // thread 0 only: the image it claims from and how many images it has not yet seen exhausted
-    int cur_img = ((int)blockIdx.x - first_wg) % nimg, left = nimg;
-    // never 1 at run time, but not provably 0 either: keeps the claim's address lane-dependent in the compiler's eyes
-    const int lane_dep = (int)(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) >> 6);
-    auto counter = [&](int img) { return claim0 + (size_t)img * claim_stride + lane_dep; };
-    auto claim_now = [&]() -> int {                                  // the next unit of cur_img, or of the next image that has one
-        while (left > 0) {
-            const int u = atomicAdd(counter(cur_img), 1);
-            if (u < units) return (cur_img << 16) | u;
-            cur_img = cur_img + 1 == nimg ? 0 : cur_img + 1;
-            --left;
-        }
-        return -1;
-    };
-    if (tid == 0) s_claim[0] = claim_now();
-    __syncthreads();
-    int cur = s_claim[0], ph = 0, staged = -1;
-    // PLAIN images (every box divides plainly, iou_tile.h -- pixel boxes always do; decided once per staging): the tile runs
-    // iou2d_rows_plain, and the lane's column boxes stay in registers from unit to unit while the wave keeps its column chunk (at
-    // N = 4096 always: a unit is one band of 16 chunks) -- gathering them, their areas and the plain test were 17 % of a tile's VALU work.
-    bool img_plain = false;
-    int cols_of = -1;                                                // the column chunk `cp` holds (of the staged image)
-    ColPairs cp;
-    const bool fast_ok = VEC && (N & 3) == 0 && (N % kStagedRows) == 0;
-    while (cur >= 0) {
-        const int img = cur >> 16, u = cur & 0xffff;
-        if (img != staged) {                                         // (every wave finished reading the old image before the last barrier)
-            const float4* b4 = reinterpret_cast<const float4*>(boxes) + (size_t)img * N;
-            bool ok = true;
-            for (int i = tid; i < N; i += 1024) { const float4 v = b4[i]; sbox[i] = v; ok = ok && box_divides_plainly(v); }
-            staged = img;
-            cols_of = -1;
-            img_plain = __syncthreads_and(ok) != 0;
-        }
-        int pre = 0;
-        const bool claims = tid == 0 && left > 0;
-        const int t = u * 16 + wave;                                 // (wave 0's tile always exists: it carries the claim)
-        if (t < ncc * nrt) {
-            const int rt = t / ncc, cc = t - rt * ncc;
-            const int c0 = cc * kWaveCols;
-            if (fast_ok && img_plain && c0 + 4 * kStagedRows <= N) { // (the first kStagedRows lanes hold the rows AND must own columns)
-                if (cc != cols_of) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) colpairs_set(cp, j, sbox[min(c0 + 4 * lane + j, N - 1)]);
-                    cols_of = cc;
-                }
-                const float4 ra = sbox[rt * kStagedRows + (lane & (kStagedRows - 1))];
-                if (c0 + 4 * lane < N) {
-                    if (claims) pre = atomicAdd(counter(cur_img), 1);                // in flight ahead of this tile's stores
-                    float* o0 = out + (size_t)img * N * ld + (size_t)(rt * kStagedRows) * ld + c0 + 4 * lane;
-                    iou2d_rows_plain<kStagedRows>(cp, ra, o0, ld);
-                    asm volatile("" :: "v"(pre));                                    // every path waits for it here: vmcnt(8) on a full tile
-                }
-            } else {
-                iou2d_tile_staged<VEC, kStagedRows>(sbox, 0, sbox + rt * kStagedRows, N, N, out + (size_t)img * N * ld, ld, rt * kStagedRows, c0, lane,
-                    [&] { if (claims) pre = atomicAdd(counter(cur_img), 1); },
-                    [&] { asm volatile("" :: "v"(pre)); });
-            }
-        }
-        if (tid == 0) {
-            int nx = -1;
-            if (left > 0) {
-                if (pre < units) nx = (cur_img << 16) | pre;
-                else { cur_img = cur_img + 1 == nimg ? 0 : cur_img + 1; --left; nx = claim_now(); }
-            }
-            s_claim[ph ^ 1] = nx;
-        }
-        __syncthreads();
-        ph ^= 1;
-        cur = s_claim[ph];
-    }
-}
-
-// SYMMETRIC writers (3D, round 3): the write role of tail_write_kernel for the cuboid overlap -- every unordered pair evaluated once
-// (iou3d_sym.h), the all-pairs 3D writers being VALU-bound at the one workgroup per CU this launch runs at (3.2e).  A persistent
-// 16-wave workgroup claims 128 x 128 macro tiles (upper triangle of every image, image-major) one claim ahead and alternates between
-// TWO LDS tiles, so that ONE barrier per macro tile suffices: it publishes the tile for the mirrored pass AND the next claim, and the
-// waves that finish their mirrored stores early already compute the next tile into the other buffer.
-template <bool NT>
-__device__ __forceinline__ void writers_sym_persistent(const float* __restrict__ rec, int N, float* __restrict__ out, long ld, int nimg, float thr,
-                                                       int* counter) {
-    using namespace gnms_iou3d;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* const tile0 = reinterpret_cast<float*>(smem);           // two LDS macro tiles, kSymTileBytes apart
-    __shared__ int s_next[2];
-    const int nt = (N + kSymT - 1) / kSymT;
-    const int tpi = sym_tiles_per_image(N), total = tpi * nimg;
-    if (threadIdx.x == 0) s_next[0] = atomicAdd(counter, 1);
-    __syncthreads();
-    int cur = s_next[0], ph = 0;
-    while (cur < total) {
-        int nx = 0;
-        if (threadIdx.x == 0) nx = atomicAdd(counter, 1);          // the claim after this one, in flight during the tile
-        const int img = cur / tpi;
-        int I, J;
-        sym_tile_of(cur - img * tpi, nt, &I, &J);
-        const float* r = rec + (size_t)img * N * kRec;
-        float* o = out + (size_t)img * N * ld;
-        float* const tile = tile0 + (size_t)ph * (kSymTileBytes / sizeof(float));
-        sym_tile_compute<16, NT>(r, N, o, ld, I, J, thr, tile);
-        if (threadIdx.x == 0) s_next[ph ^ 1] = nx;
-        __syncthreads();                                            // the tile is in LDS, the next claim is known; buffer ph ^ 1 is free
-        if (I != J) sym_tile_mirror<16, NT>(N, o, ld, I, J, tile);
-        ph ^= 1;
-        cur = s_next[ph];
-    }
-}
 
 // gnms_iou2d of a box set WITH ITSELF (what both reference call sites compute: iou(boxes, boxes)), N <= 4096: the staged writers as a
 // launch of their own -- the same claimed units, tile body and cached columns as in tail_write_kernel, the claim counters in a zeroed
@@ -936,75 +491,6 @@ int gnms_internal_iou2d_staged(const float* a, const float* b, int B, int M, int
 }
 namespace {
 
-// chain_src: what the chain's single overlaps come from (the boxes for SRC = kFromBoxes; unused for kFromRecords: the workspace copy
-// of the records); write_src: the writers' input (the boxes / the batch's contiguous records)
-template <bool VEC, int E, int SRC>
-__global__ __launch_bounds__(1024) void tail_write_kernel(const float* __restrict__ chain_src, const float* __restrict__ write_src, int N,
-                                                          const int* __restrict__ counts, gnms_params P, char* ws, gnms_ws_layout L, int Ppow2,
-                                                          float* __restrict__ prob, long long* __restrict__ valid,
-                                                          long long* __restrict__ invalid, int* __restrict__ nvalid, int* __restrict__ ninvalid,
-                                                          int nimg, float* __restrict__ out, long ld, int tile_rows, int row0, int row_end,
-                                                          int staged, int fast) {
-#ifdef GNMS_HWID    // developer experiment (tools/hwid_map.py): where the dispatcher put every workgroup of this launch
-    if (threadIdx.x == 0) {
-        unsigned* dbg = reinterpret_cast<unsigned*>(img_ptrs(ws, L, 0).rec);
-        dbg[2 * blockIdx.x] = __builtin_amdgcn_s_getreg(63492);       // HW_ID
-        dbg[2 * blockIdx.x + 1] = __builtin_amdgcn_s_getreg(63508);   // XCC_ID
-    }
-#endif
-    const int spw = leaders_chain_wgs(N, 1);                          // scan workgroups per image (the from-boxes / from-records bit matrices are symmetric)
-    const int cwg = spw + (fast ? 1 : 0);                             // + the fast tail's CSR workgroup (csr_build_body)
-    if ((int)blockIdx.x < nimg * cwg) {
-        int b;
-        GNMS_TINIT();
-#ifdef GNMS_TIMING
-        long long tt__ = (long long)__builtin_amdgcn_s_memtime();
-#define GNMS_TW_ACC(slot) do { long long n__ = (long long)__builtin_amdgcn_s_memtime(); if (threadIdx.x == 0 && b == 0) gnms::gnms_tbuf()[slot] += n__ - tt__; tt__ = n__; } while (0)
-#else
-#define GNMS_TW_ACC(slot) do {} while (0)
-#endif
-        if constexpr (E <= 4) {
-            if (fast) {                                               // masked groups: leaders_sb_body<STAGE> -> fast_final_body ‖ csr_build_body
-                if ((int)blockIdx.x >= nimg * spw) { csr_build_body<E>(N, counts, ws, L, (int)blockIdx.x - nimg * spw); return; }
-                const int last = leaders_chain<SRC>(N, counts, ws, L, nimg, spw, (int)blockIdx.x, 1, &b, chain_src, (long)N, P.nms_threshold,
-                                                    P.temperature, P.pruning_method, Ppow2);
-                if (last) { GNMS_TW_ACC(5); fast_final_body<E, SRC>(chain_src, N, (long)N, counts, P, ws, L, Ppow2, prob, valid, invalid, nvalid, ninvalid, b, last); GNMS_TW_ACC(15); }
-                GNMS_TFLUSH(ws, L, b);
-                return;
-            }
-        }
-        if (!leaders_chain(N, counts, ws, L, nimg, spw, (int)blockIdx.x, 1, &b)) return;   // (the image's other scan workgroups)
-        __syncthreads();
-        GNMS_TW_ACC(5);
-        if (E <= 4 && P.mask_group_boxes) {                           // K4's rest rides in K5 (groups_body, FUSE), K6 starts from LDS
-            if constexpr (E <= 4) {
-                GNMS_TW_ACC(6);
-                groups_body<E, SRC, true>(chain_src, N, (long)N, counts, P, ws, L, Ppow2, b);
-                gnms::lds_barrier();
-                GNMS_TW_ACC(7);
-                finalize_body<E, true>(N, counts, P, ws, L, Ppow2, prob, valid, invalid, nvalid, ninvalid, b);
-                GNMS_TW_ACC(15);
-            }
-            return;
-        } else {
-            attribute_image<SRC>(chain_src, (long)N, N, counts, P.nms_threshold, ws, L, b, 1);
-            __syncthreads();
-            GNMS_TW_ACC(6);
-            groups_body<E, SRC>(chain_src, N, (long)N, counts, P, ws, L, Ppow2, b);
-        }
-        if (!P.mask_group_boxes) return;                              // unmasked groups: the solves (a launch of their own) come before K6
-        __syncthreads();
-        GNMS_TW_ACC(7);
-        finalize_body<E>(N, counts, P, ws, L, Ppow2, prob, valid, invalid, nvalid, ninvalid, b);
-        GNMS_TW_ACC(15);
-        return;
-    }
-    const int first_writer = nimg * cwg;
-    if (SRC == kFromBoxes && staged) { writers_staged_2d<VEC>(write_src, N, out, ld, nimg, img_ptrs(ws, L, 0).misc + 5, L.per_image / sizeof(int), first_writer); return; }
-    if (SRC == kFromRecords && staged == 2) { writers_sym_persistent<true>(write_src, N, out, ld, nimg, P.nms_threshold, img_ptrs(ws, L, 0).misc + 5); return; }
-    writers_persistent<VEC, SRC>(write_src, N, out, ld, nimg, tile_rows, row0, row_end, P.nms_threshold, img_ptrs(ws, L, 0).misc + 5);
-}
-
 // gnms_forward_with_iou2d on small images as ONE launch (nms_one_launch.h): [matrix writers] [sort] [table from the boxes] [chain] [CSR].
 // The writers are writers_staged_2d with a slot of the claim ring (as iou2d_self_kernel: zero at the start, re-zeroed by the last writer
 // to leave).
@@ -1073,9 +559,11 @@ __global__ __launch_bounds__(1024) void one_launch_boxes_kernel(const float* __r
     one_launch_chain_or_csr<kFromBoxes>(boxes, N, (long)N, counts, P, ws, L, prob, valid, invalid, nvalid, ninvalid, B, bx, nsort, nbits);
 }
 
+}  // namespace
+
 // bitmask_boxes_kernel: workgroups of 4 wave tiles, (row blocks) x (column chunks) tiles per image; 4 columns per lane
 // (64 x 256 tiles) when that already gives every SIMD a couple of waves, else 1 column per lane (64 x 64 tiles)
-int launch_bitmask_boxes(const LayerCall& c, const float* boxes) {
+int gnms_internal_launch_bitmask_boxes(const LayerCall& c, const float* boxes) {
     const int B = c.B, N = c.N;
     const gnms_ws_layout& L = c.L;
     const int NB = (N + 63) / 64;
@@ -1117,13 +605,15 @@ int launch_bitmask_boxes(const LayerCall& c, const float* boxes) {
     return GNMS_OK;
 }
 
+namespace {
 // GNMS_RANK_SORT=0: 2048 < N <= 4096 sorts as runs + merge, two launches (developer / test switch, read once: the pair stays reachable for
 // A/B runs and the tests)
 bool rank_sort_enabled() { static const bool on = env_switch("GNMS_RANK_SORT", 1) != 0; return on; }
 // GNMS_HIST_SORT=0: the routing of round 8, no histogram sort (the same kind of switch)
 bool hist_sort_enabled() { static const bool on = env_switch("GNMS_HIST_SORT", 1) != 0; return on; }
+}  // namespace
 // keys in one bin from which on sort_hist_rank_kernel falls back to the run sort; gnms_profile_set_hist_cap moves it for the cap series
-std::atomic<int> g_hist_cap{kHistCap};
+std::atomic<int>& gnms_internal_hist_cap() { static std::atomic<int> cap{kHistCap}; return cap; }
 
 // K1: stable descending score sort (+ the x-centre sort of the boxes when `boxes` is given).  Which kernels (measured per call in a replayed
 // graph of 20, MI355X, LABNOTES R8.1 and R13.3; G = workgroups of the counting sort = N / 64 * B * roles, W = workgroups of the one-launch sorts
@@ -1141,7 +631,7 @@ std::atomic<int> g_hist_cap{kHistCap};
 // mode3d: 0 = `boxes` are 2D boxes (columns by x centre); >= 1 = pseudo boxes of cuboids whose records lie in the workspace (columns by
 // (z band, x centre) with that many bands; the sort also leaves the records in column order, ImgPtrs::xrec)
 // route (gnms_profile_sorts): 0 = the table above, 1 = runs + merge, 2 = ranked runs, 3 = by histogram
-int launch_sorts(const LayerCall& c, const float* scores, const float* boxes, int mode3d = 0, int route = 0) {
+int gnms_internal_launch_sorts(const LayerCall& c, const float* scores, const float* boxes, int mode3d, int route) {
     const int B = c.B, N = c.N, P2 = c.P2;
     int rc;
     const int roles = boxes ? 2 : 1;
@@ -1173,7 +663,7 @@ int launch_sorts(const LayerCall& c, const float* scores, const float* boxes, in
         const dim3 grid(kRankRuns, B, roles);
         const size_t lds = (size_t)kRankRuns * kRankRunKeys * 8;
         if (route == 3 || (route == 0 && hist))
-            sort_hist_rank_kernel<<<grid, 1024, lds, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L, (long long*)c.order, mode3d, g_hist_cap.load());
+            sort_hist_rank_kernel<<<grid, 1024, lds, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L, (long long*)c.order, mode3d, gnms_internal_hist_cap().load());
         else
             sort_ranked_runs_kernel<<<grid, 1024, lds, c.st>>>(scores, boxes, N, c.counts, c.ws, c.L, (long long*)c.order, mode3d);
         GNMS_CHECK_LAUNCH();
@@ -1206,6 +696,20 @@ int launch_sorts(const LayerCall& c, const float* scores, const float* boxes, in
     return GNMS_OK;
 }
 
+// 3D: the write role of the tail launch as symmetric writers (writers_sym_persistent) -- above N = 1024, where an image has enough
+// macro tiles.
+bool gnms::sym_writers_in_tail_launch(int N, int64_t ld, const float* out) {
+    if (!gnms_internal_overlap3d_sym_ok(N, ld, out)) return false;
+    return N > 1024;                                              // (B = 8: N = 2048 0.110 -> 0.090 ms, 1536 0.0895 -> 0.080, 1024 even)
+}
+
+// A small image's whole forward pass as ONE launch (nms_one_launch.h): masked groups, hard sort, N <= 1024 (one super-block), a 16-byte
+// aligned matrix with ld % 4 == 0, and no more workgroups than two rounds of the machine (every one asks for the chain's LDS, so a CU
+// holds one).  GNMS_ONE_LAUNCH=0: never (developer / test switch: the three-launch path stays reachable for A/B runs and the tests).
+bool gnms::one_launch_enabled() { static const bool on = env_switch("GNMS_ONE_LAUNCH", 1) != 0; return on; }
+
+namespace {
+
 // K3..K6 as one launch or four?  Measured (HIP-graph replay, B=8): one launch wins 2-2.5 us per step up to N=2048 (three
 // kernel boundaries less) and, with the general scan, loses 1.5 us at N=4096 (the attribution runs on one CU instead of 64).  Where the
 // scan attributes as it goes (symmetric sources, `sym`), K4 rides in K5 and K6 starts from LDS (groups_body FUSE, E <= 4): one launch
@@ -1221,104 +725,7 @@ bool use_tail_kernel(int N, int sym = 0) {
 // retire and stalls the chain behind the write (16 per image, 8 reserved: step 1.82 against 1.74).
 constexpr int kBesideChainWGs = 1;
 
-// K3..K6 in one launch (masked groups); SRC/src: kFromMatrix (the matrix), kFromBoxes (the boxes), kFromRecords (src unused)
-// the fast tail (nms_kernels.h): on unless GNMS_FAST_TAIL=0 (developer switch: the K5-proper path stays reachable for A/B runs and tests)
-bool fast_tail_enabled() { static const bool on = env_switch("GNMS_FAST_TAIL", 1) != 0; return on; }
-
-// dynamic LDS of the chain in tail_kernel / tail_write_kernel; P2: the launch's key count (>= 1024: the fused kernels always run 1024 threads)
-size_t tail_lds_bytes(int N, int P2, int fast) {
-    // (the fused K5 -> K6 hand-off, E <= 4, parks order[] and a copy of r2 behind the key region: 16 bytes per key)
-    const size_t llds = leaders_lds_bytes(N), glds = (size_t)P2 * (P2 <= 4096 ? 16 : 8);
-    size_t lds = llds > glds ? llds : glds;
-    if (fast && lds < fast_tail_lds_size(N, P2)) lds = fast_tail_lds_size(N, P2);
-    return lds;
-}
-
-template <int SRC>
-int launch_tail(const LayerCall& c, const float* src, int64_t ld, int sym, int chain_cap = 0) {
-    const int B = c.B, N = c.N;
-    const int P2 = c.P2 < 1024 ? 1024 : c.P2;
-    const int fast = (fast_tail_enabled() && fast_tail_ok(N, c.P, sym, chain_cap)) ? 1 : 0;
-    const size_t lds = tail_lds_bytes(N, P2, fast);
-    GNMS_CHECK_ARG(sym != 3 || fast, "launch_tail: the in-launch symmetry check needs the fast tail");
-    int rc;
-    GNMS_DISPATCH_SORT(P2, {
-        if ((rc = allow_lds(tail_kernel<E, SRC>, lds))) return rc;
-        const int spw = leaders_chain_wgs(N, sym, chain_cap);
-        // sym 3: symmetry checkers in front of the chain (one 16-wave workgroup per 128 pairs of 64 x 64 bit blocks: fewer, so that the chain workgroups behind them in the grid start sooner, at most the CUs the chain leaves)
-        int nchk = 0;
-        if (sym == 3) {
-            const long nb = (N + 63) / 64, pairs = (long)B * nb * (nb + 1) / 2;
-            const int room = gnms_device_cu_count() - B * (spw + fast);
-            nchk = (int)std::min<long>(std::max(room, 8), (pairs + 127) / 128);
-            if (nchk < 1) nchk = 1;
-        }
-        tail_kernel<E, SRC><<<nchk + B * (spw + fast), 1024, lds, c.st>>>(src, N, (long)ld, c.counts, c.P, c.ws, c.L, P2, c.prob, (long long*)c.valid, (long long*)c.invalid,
-                                                                          c.nvalid, c.ninvalid, sym, B, spw, fast, nchk);
-    });
-    GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
-}
-
-// rows per wave tile of the write role: 16 measured best at B = 8, N = 4096 (0.168 ms per step; 8: 0.174, 32: 0.175, 64: 0.193 -- the last
-// chunks of a launch end together only if chunks are short)
-constexpr int kFusedTileRows = 16;
-
-// 3D: the write role of that launch as symmetric writers (writers_sym_persistent) -- above N = 1024, where an image has enough
-// macro tiles.
-bool sym_writers_in_tail_launch(int N, int64_t ld, const float* out) {
-    if (!gnms_internal_overlap3d_sym_ok(N, ld, out)) return false;
-    return N > 1024;                                              // (B = 8: N = 2048 0.110 -> 0.090 ms, 1536 0.0895 -> 0.080, 1024 even)
-}
-
-// K3..K6 of every image + the matrix in one launch (tail_write_kernel)
-template <int SRC>
-int launch_tail_write(const LayerCall& c, const float* chain_src, const float* write_src, float* out, int64_t ld) {
-    const int B = c.B, N = c.N;
-    const int P2 = c.P2 < 1024 ? 1024 : c.P2;
-    const int fast = (fast_tail_enabled() && fast_tail_ok(N, c.P, 1)) ? 1 : 0;
-    size_t lds = tail_lds_bytes(N, P2, fast);
-    const int tr = kFusedTileRows;
-    int staged = (SRC == kFromBoxes && N <= 4096) ? 1 : 0;           // writers_staged_2d: the image's boxes in LDS
-    if (staged && lds < (size_t)N * 16) lds = (size_t)N * 16;
-    long writers = write_chunk_count(N, B, tr, 0, N);                // persistent writers: at most one per CU
-    if (SRC == kFromRecords && sym_writers_in_tail_launch(N, ld, out)) {   // writers_sym_persistent: two LDS macro tiles
-        staged = 2;
-        if (lds < 2 * gnms_iou3d::kSymTileBytes) lds = 2 * gnms_iou3d::kSymTileBytes;
-        writers = (long)gnms_iou3d::sym_tiles_per_image(N) * B;
-    }
-    const int cus = gnms_device_cu_count();
-    if (writers > cus) writers = cus;
-    // How many CUs write.  With the packed row body (iou_tile.h) a writer workgroup sustains ~29 GB/s and the stream saturates near
-    // 5.8 TB/s from ~200 of them; more writers add nothing to the matrix and slow the chain beside them, whose loads queue behind
-    // the stores.  B = 8, N = 4096, same box, ms per step clustered / uniform: 216 writers 0.140 / 0.160, 208 0.139 / 0.158,
-    // 200 0.140 / 0.151, 192 0.142 / 0.142, 184 0.144 / 0.144 -- at 24 writers per XCD the chain of the uniform images (1890
-    // leaders each) stops being the longer side of the launch, at the price of 1.5 % on clustered ones.  (A plain fill in this
-    // geometry: 6.2-6.4 TB/s from 64-128 workgroups, 5.8 from 248: profiles/r03*_store_geometry.jsonl.)
-    const int cap = staged == 1 ? (cus * 208) / 256 : 0;
-    if (cap > 0 && writers > cap) writers = cap;
-    const dim3 grid((unsigned)(B * (leaders_chain_wgs(N, 1) + fast) + writers));
-    const bool vec = (ld % 4 == 0) && ((uintptr_t)out % 16 == 0);
-    int rc;
-    GNMS_DISPATCH_SORT(P2, {
-        if (vec) {
-            if ((rc = allow_lds(tail_write_kernel<true, E, SRC>, lds))) return rc;
-            gnms_launch_prof(kProfMatrixWrite, tail_write_kernel<true, E, SRC>, grid, dim3(1024), lds, c.st, chain_src, write_src, N, c.counts, c.P, c.ws,
-                             c.L, P2, c.prob, (long long*)c.valid, (long long*)c.invalid, c.nvalid, c.ninvalid, B, out, (long)ld, tr, 0, N, staged, fast);
-        } else {
-            if ((rc = allow_lds(tail_write_kernel<false, E, SRC>, lds))) return rc;
-            gnms_launch_prof(kProfMatrixWrite, tail_write_kernel<false, E, SRC>, grid, dim3(1024), lds, c.st, chain_src, write_src, N, c.counts, c.P,
-                             c.ws, c.L, P2, c.prob, (long long*)c.valid, (long long*)c.invalid, c.nvalid, c.ninvalid, B, out, (long)ld, tr, 0, N, staged, fast);
-        }
-    });
-    GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
-}
-
-// A small image's whole forward pass as ONE launch (nms_one_launch.h): masked groups, hard sort, N <= 1024 (one super-block), a 16-byte
-// aligned matrix with ld % 4 == 0, and no more workgroups than two rounds of the machine (every one asks for the chain's LDS, so a CU
-// holds one).  GNMS_ONE_LAUNCH=0: never (developer / test switch: the three-launch path stays reachable for A/B runs and the tests).
-bool one_launch_enabled() { static const bool on = env_switch("GNMS_ONE_LAUNCH", 1) != 0; return on; }
+// the one launch of a small image (one_launch_enabled above)
 struct OneLaunchPlan { bool ok; int kpw, tpw, split; long front; };   // front: the launch's workgroups without the matrix writers
 // keys per sort workgroup with the x-order table: 64.  (Measured: 128 keys a workgroup -- two sort roles + the tables then fit one round of the
 // machine, so every table workgroup is resident from the start -- loses to the longer count: B = 8 N = 1024 31.0 against 29.7 us, B = 8 N = 768
@@ -1438,17 +845,17 @@ int forward_matrix(const LayerCall& c, const float* scores, const float* iou, in
     if ((rc = launch_one_matrix(c, scores, iou, ld, &launched)) || launched) return rc;
     const bool permute_from_boxes = boxes2d && !P.group_boxes && !P.presorted;
     // (with the boxes the score sort also leaves them in rank order, rbox; its second role, the boxes by x centre, is not used here)
-    if ((rc = launch_sorts(c, scores, permute_from_boxes ? boxes2d : nullptr))) return rc;
+    if ((rc = gnms_internal_launch_sorts(c, scores, permute_from_boxes ? boxes2d : nullptr))) return rc;
 
     if (P.group_boxes && P.mask_group_boxes && use_tail_kernel(N, matrix_sym_detection(N) ? 2 : 0)) {
         // (with the fast tail the symmetry check is a role of the tail launch and the scan runs on trust beside it: sym 3)
         const int sym = matrix_sym_detection(N) ? ((fast_tail_enabled() && fast_tail_ok(N, P, 2)) ? 3 : 2) : 0;
-        if ((rc = launch_bitmask(c, iou, ld, sym == 3 ? 2 : (sym ? 1 : 0)))) return rc;
-        return launch_tail<kFromMatrix>(c, iou, ld, sym);
+        if ((rc = gnms_internal_launch_bitmask(c, iou, ld, sym == 3 ? 2 : (sym ? 1 : 0)))) return rc;
+        return gnms_internal_launch_tail<kFromMatrix>(c, iou, ld, sym);
     }
     if (P.group_boxes) {
         const int sym = matrix_sym_detection(N) ? 2 : 0;
-        if ((rc = launch_bitmask(c, iou, ld, sym ? 1 : 0))) return rc;
+        if ((rc = gnms_internal_launch_bitmask(c, iou, ld, sym ? 1 : 0))) return rc;
         return launch_separate_tail<kFromMatrix>(c, iou, ld, sym);
     }
     float* Ps = reinterpret_cast<float*>(c.ws + (size_t)B * c.L.per_image);      // scratch behind the per-image regions
@@ -1642,7 +1049,7 @@ int forward_with_iou3d_on(const LayerCall& c, float* rec, const float* params3d,
     // about as deep in z as it is wide in x (a handful of bands of >= 512 cuboids each; one band up to N = 1024)
     // (B = 8 uniform cuboids, bit-matrix kernel: N = 4096 52 / 47 / 46 / 46.5 us with 1 / 4 / 8 / 12 bands, N = 16384 494 / 409 / 407 with 1 / 8 / 15)
     const int bands = std::max(1, std::min(8, N / 512));
-    if ((rc = launch_sorts(c, scores, xkeys, bands))) return rc;
+    if ((rc = gnms_internal_launch_sorts(c, scores, xkeys, bands))) return rc;
     SideScope scope(st);
     // the part of the write that runs beside the bit-matrix kernel: rows [0, r1) of the all-pairs kernel
     const int r1 = beside ? split_rows(N, 20) : 0;
@@ -1668,15 +1075,15 @@ int forward_with_iou3d_on(const LayerCall& c, float* rec, const float* params3d,
     }
     GNMS_CHECK_LAUNCH();
     if (chain_in_write)                                           // K3..K6 and the matrix in one launch, like the 2D entry
-        return launch_tail_write<kFromRecords>(c, nullptr, rec, iou_out, ld);
+        return gnms_internal_launch_tail_write<kFromRecords>(c, nullptr, rec, iou_out, ld);
     if (beside) {                                                 // see forward_boxes for why the fork sits exactly here
         hipStream_t side = nullptr;
         if ((rc = scope.fork(&side, 1))) return rc;
-        if ((rc = launch_tail<kFromRecords>(c, nullptr, ld, sym, kBesideChainWGs))) return rc;
+        if ((rc = gnms_internal_launch_tail<kFromRecords>(c, nullptr, ld, sym, kBesideChainWGs))) return rc;
         if ((rc = gnms_internal_nms_overlap3d(rec, B, N, iou_out, ld, side, P.nms_threshold, r1, N))) return rc;
         return scope.join();
     }
-    if (use_tail_kernel(N, sym)) return launch_tail<kFromRecords>(c, nullptr, ld, sym);
+    if (use_tail_kernel(N, sym)) return gnms_internal_launch_tail<kFromRecords>(c, nullptr, ld, sym);
     return launch_separate_tail<kFromRecords>(c, nullptr, ld, sym);
 }
 }  // namespace
@@ -1779,20 +1186,20 @@ int forward_boxes(const LayerCall& c, const float* boxes, const float* scores, c
         bool launched = false;
         if ((rc = launch_one_boxes(c, scores, boxes, mw->out, mw->ld, &launched)) || launched) return rc;
     }
-    if ((rc = launch_sorts(c, scores, boxes))) return rc;
+    if ((rc = gnms_internal_launch_sorts(c, scores, boxes))) return rc;
     if (persistent_write) {
         SideScope whole(st);
         hipStream_t side = nullptr;
-        if ((rc = launch_bitmask_boxes(c, boxes))) return rc;
+        if ((rc = gnms_internal_launch_bitmask_boxes(c, boxes))) return rc;
         if ((rc = whole.fork(&side, 0))) return rc;
         // (the scan on at most kBesideChainWGs workgroups per image: their CUs are the ones the persistent write leaves free)
-        if ((rc = launch_tail<kFromBoxes>(c, boxes, N, 1, kBesideChainWGs))) return rc;
+        if ((rc = gnms_internal_launch_tail<kFromBoxes>(c, boxes, N, 1, kBesideChainWGs))) return rc;
         if ((rc = launch_write_staged(boxes, boxes, B, N, N, mw->out, mw->ld, B * leaders_chain_wgs(N, 1, kBesideChainWGs), side))) return rc;
         return whole.join();
     }
     if (mw && mw->one_launch) {
-        if ((rc = launch_bitmask_boxes(c, boxes))) return rc;
-        if ((rc = launch_tail_write<kFromBoxes>(c, boxes, boxes, mw->out, mw->ld))) return rc;
+        if ((rc = gnms_internal_launch_bitmask_boxes(c, boxes))) return rc;
+        if ((rc = gnms_internal_launch_tail_write<kFromBoxes>(c, boxes, boxes, mw->out, mw->ld))) return rc;
         if (P.mask_group_boxes) return GNMS_OK;
         // unmasked groups: the chain stopped behind K5's group structure
         if ((rc = launch_solve_groups<kForward, kFromBoxes>(c, boxes, N, nullptr, nullptr))) return rc;
@@ -1805,7 +1212,7 @@ int forward_boxes(const LayerCall& c, const float* boxes, const float* scores, c
         if ((rc = beside.fork(&side, 0))) return rc;
         if ((rc = gnms_internal_iou2d_rows(boxes, B, N, mw->out, mw->ld, side, 0, r1))) return rc;
     }
-    if ((rc = launch_bitmask_boxes(c, boxes))) return rc;
+    if ((rc = gnms_internal_launch_bitmask_boxes(c, boxes))) return rc;
     if (mw) {
         // Large images: the rest of the layer is one workgroup per image (K3..K6 in one launch) and the matrix write runs beside
         // it on the side stream.  The write is forked HERE and not earlier because its workgroups take every free wave slot: a
@@ -1814,12 +1221,12 @@ int forward_boxes(const LayerCall& c, const float* boxes, const float* scores, c
         // the event (same-queue successor ~2 us, cross-queue event ~25 us), and then keep their CUs until the layer is done.
         hipStream_t side = nullptr;
         if ((rc = beside.fork(&side, 1))) return rc;
-        if ((rc = launch_tail<kFromBoxes>(c, boxes, N, 1, kBesideChainWGs))) return rc;
+        if ((rc = gnms_internal_launch_tail<kFromBoxes>(c, boxes, N, 1, kBesideChainWGs))) return rc;
         if ((rc = gnms_internal_iou2d_rows(boxes, B, N, mw->out, mw->ld, side, r1, N))) return rc;
         return beside.join();
     }
     // (sym 1: bitmask_boxes_kernel wrote full symmetric rows)
-    if (P.mask_group_boxes && use_tail_kernel(N, 1)) return launch_tail<kFromBoxes>(c, boxes, N, 1);
+    if (P.mask_group_boxes && use_tail_kernel(N, 1)) return gnms_internal_launch_tail<kFromBoxes>(c, boxes, N, 1);
     return launch_separate_tail<kFromBoxes>(c, boxes, N, 1);
 }
 }  // namespace
@@ -1908,98 +1315,6 @@ extern "C" int gnms_backward_boxes(const float* grad_prob, const float* boxes, c
                                stream);
 }
 
-// Profiling hook: re-runs ONLY the threshold bit-matrix kernel (K2, the one full read of the matrix) on a
-// workspace that a previous gnms_forward filled (it needs `order`).  bench.py times it for the roofline line.
-extern "C" int gnms_profile_bitmask(const float* iou, int B, int N, int64_t ld, const int32_t* counts, float nms_threshold,
-                                    void* workspace, size_t workspace_bytes, void* stream) {
-    gnms_params P;
-    gnms_default_params(&P);
-    int rc = check_common("gnms_profile_bitmask", B, N, ld, &P, workspace, workspace_bytes);
-    if (rc) return rc;
-    if (B == 0 || N == 0) return GNMS_OK;
-    P.nms_threshold = nms_threshold;
-    return launch_bitmask(make_call(B, N, counts, P, workspace, stream), iou, ld);
-}
-
-extern "C" int gnms_profile_bitmask_boxes(const float* boxes, int B, int N, const int32_t* counts, float nms_threshold, void* workspace,
-                                          size_t workspace_bytes, void* stream) {
-    gnms_params P;
-    gnms_default_params(&P);
-    int rc = check_common("gnms_profile_bitmask_boxes", B, N, N, &P, workspace, workspace_bytes);
-    if (rc) return rc;
-    if (B == 0 || N == 0) return GNMS_OK;
-    P.nms_threshold = nms_threshold;
-    return launch_bitmask_boxes(make_call(B, N, counts, P, workspace, stream), boxes);
-}
-
-// Profiling / test hook: ONLY the sorts (K1) of the 2D layer, on a chosen route, and what they leave in the workspace copied out.
-namespace {
-__global__ void export_sorts_kernel(int N, const int* __restrict__ counts, char* ws, gnms_ws_layout L, int has_boxes, int* __restrict__ order,
-                                    int* __restrict__ rankof, float* __restrict__ sscore, float4* __restrict__ rbox, int* __restrict__ xidx,
-                                    float4* __restrict__ xbox, int* __restrict__ flags) {
-    using namespace gnms;
-    const int b = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = gnms_count(counts, b, N);
-    ImgPtrs I = img_ptrs(ws, L, b);
-    if (k == 0 && flags) { flags[2 * b] = I.misc[2]; flags[2 * b + 1] = has_boxes ? I.misc[6] : 0; }
-    if (k >= N) return;
-    const size_t o = (size_t)b * N + k;
-    if (order) order[o] = I.order[k];
-    if (rankof) rankof[o] = I.rankof[k];
-    if (sscore) sscore[o] = I.sscore[k];
-    // (the sorts write these for the image's n boxes only: zeros behind them)
-    const bool live = has_boxes && k < n;
-    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (rbox) rbox[o] = live ? I.rbox[k] : zero;
-    if (xidx) xidx[o] = live ? I.xidx[k] : 0;
-    if (xbox) xbox[o] = live ? I.xbox[k] : zero;
-}
-}  // namespace
-
-extern "C" int gnms_profile_sorts(const float* scores, const float* boxes, int B, int N, const int32_t* counts, int route, int32_t* order,
-                                  int32_t* rankof, float* sscore, float* rbox, int32_t* xidx, float* xbox, int32_t* flags, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-    gnms_params P;
-    gnms_default_params(&P);
-    int rc = check_common("gnms_profile_sorts", B, N, N, &P, workspace, workspace_bytes);
-    if (rc) return rc;
-    GNMS_CHECK_ARG(route >= 0 && route <= 3, "gnms_profile_sorts: route %d (0 default, 1 runs + merge, 2 ranked runs, 3 by histogram)", route);
-    if (B == 0 || N == 0) return GNMS_OK;
-    GNMS_CHECK_ARG(scores != nullptr, "gnms_profile_sorts: scores is NULL");
-    const LayerCall c = make_call(B, N, counts, P, workspace, stream);
-    if ((rc = launch_sorts(c, scores, boxes, 0, route))) return rc;
-    if (order || rankof || sscore || rbox || xidx || xbox || flags) {
-        export_sorts_kernel<<<dim3(gnms_div_up(N, 256), B), 256, 0, c.st>>>(N, counts, c.ws, c.L, boxes ? 1 : 0, order, rankof, sscore,
-                                                                          (float4*)rbox, xidx, (float4*)xbox, flags);
-        GNMS_CHECK_LAUNCH();
-    }
-    return GNMS_OK;
-}
-
-namespace {
-__global__ void export_sort_paths_kernel(char* ws, gnms_ws_layout L, int B, int32_t* __restrict__ paths) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 2 * B) paths[i] = gnms::img_ptrs(ws, L, i >> 1).misc[gnms::kSortPathSlot + (i & 1)];
-}
-}  // namespace
-
-extern "C" int gnms_profile_sort_paths(int B, int N, int32_t* paths, int32_t* cap_out, void* workspace, size_t workspace_bytes, void* stream) {
-    gnms_params P;
-    gnms_default_params(&P);
-    int rc = check_common("gnms_profile_sort_paths", B, N, N, &P, workspace, workspace_bytes);
-    if (rc) return rc;
-    if (cap_out) *cap_out = g_hist_cap.load();
-    if (B == 0 || N == 0 || !paths) return GNMS_OK;
-    const LayerCall c = make_call(B, N, nullptr, P, workspace, stream);
-    export_sort_paths_kernel<<<gnms_div_up(2 * B, 64), 64, 0, c.st>>>(c.ws, c.L, B, paths);
-    GNMS_CHECK_LAUNCH();
-    return GNMS_OK;
-}
-
-extern "C" int gnms_profile_set_hist_cap(int cap) {
-    return g_hist_cap.exchange(cap < 0 ? gnms::kHistCap : std::min(cap, gnms::kHistCapMax));
-}
-
 // ------------------------------------------------------------------------------------------------
 // get_groups as a stand-alone entry (lib/groomed_nms.py:208-270)
 // ------------------------------------------------------------------------------------------------
@@ -2046,7 +1361,7 @@ extern "C" int gnms_get_groups(const float* scores, const float* iou, int N, int
     GNMS_CHECK_LAUNCH();
     // grouping pipeline K2..K5, as the unmasked layer runs it
     const int sym = matrix_sym_detection(N) ? 2 : 0;
-    if ((rc = launch_bitmask(c, iou, ld, sym ? 1 : 0))) return rc;
+    if ((rc = gnms_internal_launch_bitmask(c, iou, ld, sym ? 1 : 0))) return rc;
     if ((rc = launch_leaders_attribute<kFromMatrix>(c, iou, ld, sym))) return rc;
     if ((rc = launch_groups<kFromMatrix>(c, iou, ld))) return rc;
     export_groups_kernel<<<gnms_div_up(N, 256), 256, 0, st>>>(N, c.ws, c.L, group_of, pos_in_group, ngroups_out);

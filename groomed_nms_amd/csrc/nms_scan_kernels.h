@@ -1,6 +1,7 @@
 // nms_scan_kernels.h -- K3 of the GrooMeD-NMS layer: the leader scan (= the boxes classical greedy NMS keeps) on the threshold bit
 // matrix W, as the general scan of one workgroup per image (leaders_body) and as the chain of one workgroup per super-block for a
-// symmetric matrix (leaders_sb_body).  Shared by the layer (nms_kernels.h) and classic_nms.hip, which both launch leaders_kernel.
+// symmetric matrix (leaders_sb_body).  Shared by the layer (nms_kernels.h) and classic_nms.hip; the scan as a launch of its own,
+// leaders_kernel, is in nms_leaders_kernel.h (nms_layer.hip and classic_nms.hip launch it, the tail units only use the bodies).
 #pragma once
 #include "gnms_device.h"
 
@@ -120,7 +121,7 @@ __device__ __forceinline__ void leaders_epilogue(const ImgPtrs& I, const u64* lm
 // agent-scope loads: a granule is valid iff its tag is the workspace's call counter (misc[8], advanced by the sort kernels of every
 // call -- so stale granules of earlier calls, or of earlier replays of a captured graph, never match; the same kernels also zero the
 // image's granules, so that whatever a recycled allocation held where they now lie cannot carry the tag by accident).
-// No fence anywhere: beside the matrix writers one agent-scope release costs more than the whole scan (nms_layer.hip).  rem[] goes
+// No fence anywhere: beside the matrix writers one agent-scope release costs more than the whole scan (nms_writers.h).  rem[] goes
 // out through write-through stores as well and is read back (groups_body / attribute_*) with agent-scope loads; the workgroup of the
 // LAST super-block waits for the other workgroups' "rem stored" granules and carries on with K4..K6 of the image.
 // A workgroup only ever waits for workgroups with a LOWER block index (dispatched before it).
@@ -693,12 +694,6 @@ __device__ __forceinline__ int leaders_chain(int N, const int* __restrict__ coun
     const int j0 = jw * q, j1 = min(nsb, j0 + q);
     if (j0 >= j1) return 0;                                        // (workgroup-uniform)
     return leaders_sb_body<STAGE>(N, counts, ws, L, b, j0, j1, jw, stage_src, stage_ld, stage_thr, stage_temp, stage_prune, Ppow2, 0u, 0, 0, ext0);
-}
-
-__global__ __launch_bounds__(1024) void leaders_kernel(int N, const int* __restrict__ counts, char* ws, gnms_ws_layout L, int sym, int B, int spw,
-                                                       const u64* __restrict__ ext0 = nullptr) {
-    int b;
-    leaders_chain(N, counts, ws, L, B, spw, (int)blockIdx.x, sym, &b, nullptr, 0, 0.0f, 0.0f, 0, 0, ext0);
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 #!/bin/bash
 # VGPR / SGPR / LDS / occupancy of every kernel of one translation unit (gfx950), from the compiler's own remarks.
-#   tools/kernel_resources.sh nms_layer.hip [filter]
+#   tools/kernel_resources.sh nms_layer.hip [filter]          (tail_kernel / tail_write_kernel: nms_tail_<source>.hip / nms_tail_write_<source>.hip)
 src=groomed_nms_amd/csrc/$1
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -c "$src" -o /dev/null \
     -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c '

@@ -5,7 +5,7 @@
 #include <stdlib.h>
 #include <math.h>
 #include <vector>
-#include "nms_kernels.h"
+#include "nms_layer_kernels.h"   // nms_kernels.h + the layer's non-template kernels (leaders_kernel, ...)
 using namespace gnms;
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
