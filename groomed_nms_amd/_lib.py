@@ -70,6 +70,7 @@ _SIGNATURES = {
                                                             ctypes.c_int]),
     "gnms_backward_boxes": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.POINTER(GnmsParams), c_vp, c_vp, c_vp,
                                            ctypes.c_int64, ctypes.c_int, c_vp, ctypes.c_size_t, c_vp, ctypes.c_size_t, c_vp]),
+    "gnms_backward_reads": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GnmsParams), c_vp, ctypes.c_int]),
     "gnms_profile_bitmask": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, ctypes.c_float, c_vp,
                                             ctypes.c_size_t, c_vp]),
     "gnms_profile_bitmask_boxes": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_float, c_vp, ctypes.c_size_t, c_vp]),

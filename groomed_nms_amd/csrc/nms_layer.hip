@@ -192,6 +192,41 @@ size_t tail_lds_bytes(int N, int P2, int fast) {
 
 using namespace gnms;
 
+namespace {
+// The gates of the forward and backward entries, each written ONCE: the entries below branch on them and gnms_backward_reads answers
+// from them, so what a binding keeps for the backward cannot drift from what the library runs.
+bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }                 // the from-boxes kernels load a box as one float4
+bool masked_groups(const gnms_params& P) { return P.group_boxes && P.mask_group_boxes; }   // their backward reads no overlap
+// gnms_forward_with_iou2d runs the layer from the boxes (gnms_backward_from_boxes can follow when the groups are unmasked)
+bool from_boxes_2d(const gnms_params& P, const void* boxes) { return P.group_boxes && !P.presorted && aligned16(boxes); }
+// gnms_forward_with_iou3d runs the layer from the cuboid records
+bool from_records_3d(const gnms_params& P) { return masked_groups(P) && !P.presorted; }
+// masked groups, hard sort, unsorted output (the default mode): gnms_backward fuses its first pass into the masked kernel, and
+// gnms_backward_boxes has one matrix-gradient entry per non-head member -- no N x N pass
+bool masked_default(const gnms_params& P) { return masked_groups(P) && !P.return_sorted_prob && !P.presorted; }
+bool boxes_sparse_route(const gnms_params& P, int route) { return route == GNMS_BOXES_ROUTE_AUTO && masked_default(P); }
+}  // namespace
+
+// host code only (the gate table stands in include/groomed_nms_hip.h)
+extern "C" int gnms_backward_reads(int entry, const gnms_params* params, const void* boxes, int box_grad_route) {
+    GNMS_CHECK_ARG(entry >= GNMS_ENTRY_MATRIX && entry <= GNMS_ENTRY_FROM_BOXES, "gnms_backward_reads: unknown entry %d", entry);
+    GNMS_CHECK_ARG(params != nullptr, "gnms_backward_reads: params is NULL");
+    GNMS_CHECK_ARG(boxes != nullptr || entry == GNMS_ENTRY_MATRIX, "gnms_backward_reads: boxes is NULL");
+    const gnms_params& P = *params;
+    if (box_grad_route != GNMS_BOXES_ROUTE_NONE) {
+        GNMS_CHECK_ARG(box_grad_route == GNMS_BOXES_ROUTE_AUTO || box_grad_route == GNMS_BOXES_ROUTE_DENSE, "gnms_backward_reads: unknown route %d",
+                       box_grad_route);
+        GNMS_CHECK_ARG(entry == GNMS_ENTRY_WITH_IOU2D || entry == GNMS_ENTRY_FROM_BOXES,
+                       "gnms_backward_reads: gnms_backward_boxes follows gnms_forward_with_iou2d / gnms_forward_from_boxes only");
+        return GNMS_BWD_READS_BOXES | (boxes_sparse_route(P, box_grad_route) ? 0 : GNMS_BWD_READS_MATRIX) | (aligned16(boxes) ? 0 : GNMS_BWD_COPY_BOXES);
+    }
+    if (entry == GNMS_ENTRY_MATRIX) return GNMS_BWD_READS_MATRIX;
+    if (entry == GNMS_ENTRY_FROM_BOXES) return GNMS_BWD_READS_BOXES | GNMS_BWD_FROM_BOXES;
+    if (masked_groups(P)) return 0;
+    if (entry == GNMS_ENTRY_WITH_IOU2D && from_boxes_2d(P, boxes)) return GNMS_BWD_READS_BOXES | GNMS_BWD_FROM_BOXES;
+    return GNMS_BWD_READS_MATRIX;
+}
+
 // full: 0 = only the words a leader scan reads; 1 = whole rows + wsym_check_kernel behind; 2 = whole rows, the check rides in the tail launch
 int gnms_internal_launch_bitmask(const LayerCall& c, const float* iou, int64_t ld, int full) {
     const int B = c.B, N = c.N;
@@ -847,7 +882,7 @@ int forward_matrix(const LayerCall& c, const float* scores, const float* iou, in
     // (with the boxes the score sort also leaves them in rank order, rbox; its second role, the boxes by x centre, is not used here)
     if ((rc = gnms_internal_launch_sorts(c, scores, permute_from_boxes ? boxes2d : nullptr))) return rc;
 
-    if (P.group_boxes && P.mask_group_boxes && use_tail_kernel(N, matrix_sym_detection(N) ? 2 : 0)) {
+    if (masked_groups(P) && use_tail_kernel(N, matrix_sym_detection(N) ? 2 : 0)) {
         // (with the fast tail the symmetry check is a role of the tail launch and the scan runs on trust beside it: sym 3)
         const int sym = matrix_sym_detection(N) ? ((fast_tail_enabled() && fast_tail_ok(N, P, 2)) ? 3 : 2) : 0;
         if ((rc = gnms_internal_launch_bitmask(c, iou, ld, sym == 3 ? 2 : (sym ? 1 : 0)))) return rc;
@@ -998,7 +1033,7 @@ extern "C" int gnms_forward_with_iou2d(const float* boxes, const float* scores, 
     GNMS_BEGIN_CALL("gnms_forward_with_iou2d", &c, B, N, ld, counts, params, workspace, workspace_bytes, stream, false,
                     boxes && scores && iou_out && prob, "gnms_forward_with_iou2d: null pointer", prob, order, valid, invalid, nvalid, ninvalid);
     const gnms_params& P = c.P;
-    const bool from_boxes = P.group_boxes && !P.presorted && ((uintptr_t)boxes % 16 == 0);
+    const bool from_boxes = from_boxes_2d(P, boxes);
     const bool beside = from_boxes && P.mask_group_boxes && use_side_stream(B, N, ld);
     // masked from-boxes layer, no side stream: K3..K6 of every image and the matrix write as ONE launch (tail_write_kernel), always
     // (up to N = 1024 the score / x sorts could ride in the IoU launch instead, rounds 1-3's iou2d_sort_kernel; replayed as a HIP graph -- the GPU's
@@ -1015,7 +1050,7 @@ extern "C" int gnms_forward_with_iou2d(const float* boxes, const float* scores, 
     int rc;
     if ((rc = gnms_iou2d(boxes, boxes, B, N, N, iou_out, ld, stream))) return rc;
     if (from_boxes) return forward_boxes(c, boxes, scores);
-    return forward_matrix(c, scores, iou_out, ld, ((uintptr_t)boxes % 16 == 0) ? boxes : nullptr);
+    return forward_matrix(c, scores, iou_out, ld, aligned16(boxes) ? boxes : nullptr);
 }
 
 // defined in iou_kernels.hip
@@ -1033,7 +1068,7 @@ int forward_with_iou3d_on(const LayerCall& c, float* rec, const float* params3d,
     const gnms_params& P = c.P;
     const gnms_ws_layout& L = c.L;
     hipStream_t st = c.st;
-    const bool from_rec = P.group_boxes && P.mask_group_boxes && !P.presorted;
+    const bool from_rec = from_records_3d(P);
     int rc;
     if (!from_rec) {
         if ((rc = gnms_internal_records_from_params(params3d, (long)B * N, rec, st))) return rc;
@@ -1107,7 +1142,7 @@ extern "C" int gnms_forward_with_iou3d(const float* params3d, const float* score
     const hipError_t fe = hipFreeAsync(rec, c.st);                // after the side stream, if any, has joined `st`
     if (rc) return rc;
     if (fe != hipSuccess) { gnms_set_error("hipFreeAsync failed: %s", hipGetErrorString(fe)); return GNMS_ERR_HIP; }
-    if (!(c.P.group_boxes && c.P.mask_group_boxes && !c.P.presorted)) return forward_matrix(c, scores, iou_out, ld);
+    if (!from_records_3d(c.P)) return forward_matrix(c, scores, iou_out, ld);
     return GNMS_OK;
 }
 
@@ -1123,13 +1158,13 @@ extern "C" int gnms_backward(const float* grad_prob, const float* scores, const 
     hipStream_t st = c.st;
     int rc;
     dim3 ge(gnms_div_up(N, 256), B);
-    const bool fused_gx = P.group_boxes && P.mask_group_boxes && !P.return_sorted_prob && !P.presorted;   // the default path
+    const bool fused_gx = masked_default(P);
     if (!fused_gx) {
         bwd_gx_kernel<<<ge, 256, 0, st>>>(grad_prob, N, counts, P, ws, L);
         GNMS_CHECK_LAUNCH();
     }
     if (grad_iou) GNMS_CHECK_HIP(hipMemsetAsync(grad_iou, 0, sizeof(float) * (size_t)B * N * ld, st));
-    if (P.group_boxes && P.mask_group_boxes) {
+    if (masked_groups(P)) {
         const int head_blocks = N >= 2048 ? 128 : gnms_div_up(N, 16);
         // GNMS_BWD_PLAN=0: the backward that walks hlist / gstart / glen / gsorted instead of the forward's plan (A/B runs, the bit-for-bit test)
         static const bool by_plan = env_switch("GNMS_BWD_PLAN", 1) != 0;
@@ -1237,7 +1272,7 @@ extern "C" int gnms_forward_from_boxes(const float* boxes, const float* scores, 
     LayerCall c;
     GNMS_BEGIN_CALL("gnms_forward_from_boxes", &c, B, N, N, counts, params, workspace, workspace_bytes, stream, true, boxes && scores && prob,
                     "gnms_forward_from_boxes: null boxes/scores/prob", prob, order, valid, invalid, nvalid, ninvalid);
-    GNMS_CHECK_ARG((uintptr_t)boxes % 16 == 0, "gnms_forward_from_boxes: boxes must be 16-byte aligned");
+    GNMS_CHECK_ARG(aligned16(boxes), "gnms_forward_from_boxes: boxes must be 16-byte aligned");
     return forward_boxes(c, boxes, scores);
 }
 
@@ -1258,10 +1293,6 @@ extern "C" int gnms_backward_from_boxes(const float* grad_prob, const float* box
 // backward with the gradient w.r.t. the boxes
 // ------------------------------------------------------------------------------------------------
 namespace {
-// masked groups, hard sort, unsorted output: one matrix-gradient entry per non-head member, no N x N pass
-bool boxes_sparse_route(const gnms_params& P, int route) {
-    return route == GNMS_BOXES_ROUTE_AUTO && P.group_boxes && P.mask_group_boxes && !P.return_sorted_prob && !P.presorted;
-}
 struct BoxesScratch { size_t grad_iou, iou, reduce, total; };
 BoxesScratch boxes_scratch(int B, int N, int64_t ld, bool have_iou) {
     BoxesScratch s;
@@ -1285,7 +1316,7 @@ extern "C" int gnms_backward_boxes(const float* grad_prob, const float* boxes, c
     GNMS_CHECK_ARG(route == GNMS_BOXES_ROUTE_AUTO || route == GNMS_BOXES_ROUTE_DENSE, "gnms_backward_boxes: unknown route %d", route);
     GNMS_BEGIN_CALL("gnms_backward_boxes", &c, B, N, ld, counts, params, workspace, workspace_bytes, stream, false,
                     grad_prob && boxes && scores && grad_scores && grad_boxes, "gnms_backward_boxes: null pointer");
-    GNMS_CHECK_ARG(((uintptr_t)boxes % 16 == 0) && ((uintptr_t)grad_boxes % 16 == 0), "gnms_backward_boxes: boxes and grad_boxes must be 16-byte aligned");
+    GNMS_CHECK_ARG(aligned16(boxes) && aligned16(grad_boxes), "gnms_backward_boxes: boxes and grad_boxes must be 16-byte aligned");
     if (boxes_sparse_route(c.P, route)) {
         // (the masked backward never dereferences the matrix pointer when no matrix gradient is asked for)
         const int rc = gnms_backward(grad_prob, scores, boxes, B, N, N, counts, params, grad_scores, nullptr, workspace, workspace_bytes, stream);

@@ -32,7 +32,7 @@ void check(int rc, const char* what) {
 }
 
 // which entry runs the forward pass
-enum Mode : int64_t { kMatrixIn = 0, kWithIou2d = 1, kWithIou3d = 2, kFromBoxes = 3 };
+enum Mode : int64_t { kMatrixIn = GNMS_ENTRY_MATRIX, kWithIou2d = GNMS_ENTRY_WITH_IOU2D, kWithIou3d = GNMS_ENTRY_WITH_IOU3D, kFromBoxes = GNMS_ENTRY_FROM_BOXES };
 
 using DeviceGuard = c10::hip::HIPGuardMasqueradingAsCUDA;
 inline hipStream_t current_stream(const Tensor& t) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream(); }
@@ -79,43 +79,40 @@ struct Layer : public torch::autograd::Function<Layer> {
         int32_t* const ni_out = tl_counts_slot ? tl_counts_slot + B : (int32_t*)mptr(ninvalid);
         const size_t wsb = gnms_workspace_bytes((int)B, (int)N, &P);
         Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 256)}, f32.dtype(at::kByte));
-        Tensor kept, iou;                     // kept: what the backward reads besides the scores (matrix / boxes), if anything
-        bool bwd_boxes = mode == kFromBoxes;  // the backward takes its overlaps from `kept` = boxes
+        Tensor boxes, matrix, iou;            // boxes / matrix: what the backward may read besides the scores; iou: the matrix as an output
         int64_t ld = std::max<int64_t>(N, 1);
         if (mode == kMatrixIn) {
             TORCH_CHECK(src.size(2) == N, "GNMS: iou must be [B, N, N]");
             auto ml = matrix_layout(src);
-            kept = ml.first;
+            matrix = ml.first;
             ld = ml.second;
-            check(gnms_forward((const float*)cptr(s), (const float*)cptr(kept), (int)B, (int)N, ld, (const int32_t*)cptr(counts), &P, (float*)mptr(prob),
+            check(gnms_forward((const float*)cptr(s), (const float*)cptr(matrix), (int)B, (int)N, ld, (const int32_t*)cptr(counts), &P, (float*)mptr(prob),
                                (int64_t*)mptr(order), (int64_t*)mptr(valid), (int64_t*)mptr(invalid), nv_out, ni_out,
                                mptr(ws), (size_t)ws.numel(), st), "gnms_forward");
         } else if (mode == kFromBoxes) {
             TORCH_CHECK(src.size(2) == 4, "GNMS: boxes must be [B, N, 4]");
-            kept = src.contiguous();
-            check(gnms_forward_from_boxes((const float*)cptr(kept), (const float*)cptr(s), (int)B, (int)N, (const int32_t*)cptr(counts), &P, (float*)mptr(prob),
+            boxes = src.contiguous();
+            check(gnms_forward_from_boxes((const float*)cptr(boxes), (const float*)cptr(s), (int)B, (int)N, (const int32_t*)cptr(counts), &P, (float*)mptr(prob),
                                           (int64_t*)mptr(order), (int64_t*)mptr(valid), (int64_t*)mptr(invalid), nv_out,
                                           ni_out, mptr(ws), (size_t)ws.numel(), st), "gnms_forward_from_boxes");
         } else {
             const bool three_d = mode == kWithIou3d;
             TORCH_CHECK(src.size(2) == (three_d ? 7 : 4), "GNMS: expected [B, N, ", three_d ? 7 : 4, "] as the second argument");
-            Tensor boxes = src.contiguous();
-            iou = iou_out_.has_value() ? *iou_out_ : at::empty({B, N, N}, f32);
+            boxes = src.contiguous();
+            matrix = iou = iou_out_.has_value() ? *iou_out_ : at::empty({B, N, N}, f32);
             TORCH_CHECK(iou.is_cuda() && iou.scalar_type() == at::kFloat && iou.is_contiguous() && iou.numel() == B * N * N, "GNMS: iou_out must be a contiguous CUDA float [B, N, N] tensor");
             auto entry = three_d ? gnms_forward_with_iou3d : gnms_forward_with_iou2d;
             check(entry((const float*)cptr(boxes), (const float*)cptr(s), (int)B, (int)N, ld, (const int32_t*)cptr(counts), &P, (float*)mptr(iou),
                         (float*)mptr(prob), (int64_t*)mptr(order), (int64_t*)mptr(valid), (int64_t*)mptr(invalid), nv_out,
                         ni_out, mptr(ws), (size_t)ws.numel(), st), three_d ? "gnms_forward_with_iou3d" : "gnms_forward_with_iou2d");
-            // The masked-group backward (the default) never reads the overlaps, so the matrix is not kept at all.  The unmasked / ungrouped
-            // backward does: there it is saved through autograd, whose version counter then catches a caller that overwrites the
-            // (possibly caller-provided) buffer between forward and backward instead of silently producing wrong gradients.
-            // Grouped unmasked 2D: the backward solves its groups from the BOXES (gnms_backward_from_boxes: bit-identical overlaps, no matrix
-            // reads, a caller may reuse iou_out at once); only the ungrouped mode and the 3D entry still read the matrix back.
-            // (the same predicate as gnms_forward_with_iou2d's from-boxes gate, alignment included: for an unaligned view of the boxes the forward took
-            // the matrix path, and the backward must not run float4 loads on that pointer -- ADVICE r4)
-            if (!three_d && group && !mask && !presorted && (reinterpret_cast<uintptr_t>(boxes.data_ptr()) % 16 == 0)) { kept = boxes; bwd_boxes = true; }
-            else if (!(group && mask)) kept = iou;
         }
+        // What the backward will read, and which entry it is, is the library's answer (gnms_backward_reads; the gate table stands in
+        // groomed_nms_hip.h).  A matrix that is kept is saved through autograd, whose version counter then catches a caller that overwrites the
+        // (possibly caller-provided) buffer between forward and backward instead of silently producing wrong gradients; one that is not
+        // kept may be reused at once.  (an empty call reads nothing, and has no pointer to ask about)
+        const int reads = s.numel() ? gnms_backward_reads((int)mode, &P, cptr(boxes), GNMS_BOXES_ROUTE_NONE) : 0;
+        if (reads < 0) check(reads, "gnms_backward_reads");
+        Tensor kept = (reads & GNMS_BWD_READS_BOXES) ? boxes : (reads & GNMS_BWD_READS_MATRIX) ? matrix : Tensor();
         ctx->set_materialize_grads(false);                               // no zero-filled "gradients" for the index outputs
         ctx->saved_data["mode"] = mode;
         ctx->saved_data["ld"] = ld;
@@ -123,7 +120,7 @@ struct Layer : public torch::autograd::Function<Layer> {
                                                         (double)presorted};
         ctx->saved_data["has_counts"] = counts.defined();
         ctx->saved_data["has_kept"] = kept.defined();
-        ctx->saved_data["bwd_boxes"] = bwd_boxes;
+        ctx->saved_data["bwd_boxes"] = (reads & GNMS_BWD_FROM_BOXES) != 0;
         variable_list saved{s, ws};
         if (counts.defined()) saved.push_back(counts);
         if (kept.defined()) saved.push_back(kept);

@@ -124,241 +124,103 @@ def _matrix_layout(iou):
     return iou.contiguous(), N
 
 
-class _GroomedNMSFunction(torch.autograd.Function):
-    """prob = GrooMeD-NMS(scores, iou); gradients w.r.t. scores and (only if it requires grad) iou.
-    The reference differentiates the same graph with autograd (lib/groomed_nms.py:111)."""
-
-    @staticmethod
-    def forward(ctx, scores, iou, counts, params):
-        lib = _lib.load()
-        B, N = scores.shape
-        dev = scores.device
-        scores_c = scores.contiguous()
-        iou_c, ld = _matrix_layout(iou)
-        prob, order, valid, invalid, nvalid, ninvalid = _outputs(B, N, dev, getattr(params, "index_lists", True))
-        nbytes = _workspace_bytes(lib, B, N, params)
-        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-        with on_device(dev):
-            check(lib.gnms_forward(ptr(scores_c), ptr(iou_c), B, N, ld, ptr(counts), ctypes.byref(params), ptr(prob), ptr(order),
-                                   ptr(valid), ptr(invalid), ptr(nvalid), ptr(ninvalid), ptr(ws), ws.numel(), stream_ptr(dev)),
-                  "gnms_forward")
-        ctx.params = params
-        ctx.ld = ld
-        ctx.set_materialize_grads(False)      # no zero-filled "gradients" for the five index outputs
-        ctx.save_for_backward(scores_c, iou_c, counts, ws)
-        ctx.mark_non_differentiable(*[x for x in (order, valid, invalid, nvalid, ninvalid) if x is not None])
-        return prob, order, valid, invalid, nvalid, ninvalid
-
-    @staticmethod
-    def backward(ctx, grad_prob, *unused):
-        lib = _lib.load()
-        scores_c, iou_c, counts, ws = ctx.saved_tensors
-        B, N = scores_c.shape
-        dev = scores_c.device
-        if grad_prob is None:
-            return None, None, None, None
-        grad_prob = grad_prob.contiguous().float()
-        grad_scores = torch.empty_like(scores_c)
-        grad_iou = None
-        if ctx.needs_input_grad[1]:
-            grad_iou = torch.empty((B, N, ctx.ld), dtype=torch.float32, device=dev)
-        with on_device(dev):
-            check(lib.gnms_backward(ptr(grad_prob), ptr(scores_c), ptr(iou_c), B, N, ctx.ld, ptr(counts), ctypes.byref(ctx.params),
-                                    ptr(grad_scores), ptr(grad_iou), ptr(ws), ws.numel(), stream_ptr(dev)), "gnms_backward")
-        if grad_iou is not None and ctx.ld != N:
-            grad_iou = grad_iou[:, :, :N]
-        return grad_scores, grad_iou, None, None
-
-
-class _GroomedNMSWithIouFunction(torch.autograd.Function):
-    """(prob, ..., iou) = 2D IoU matrix + GrooMeD-NMS in one library call (gnms_forward_with_iou2d): same results as
-    overlaps.iou_batched followed by _GroomedNMSFunction; in the grouped modes the layer runs from the boxes beside the matrix write.  The matrix comes
-    back detached, as the reference's loss feeds it (lib/loss/rpn_3d.py:791 `.clone().detach()`)."""
-
-    @staticmethod
-    def forward(ctx, scores, boxes, counts, params, iou_out):
-        lib = _lib.load()
-        B, N = scores.shape
-        dev = scores.device
-        scores_c = scores.contiguous()
-        boxes_c = boxes.contiguous()
-        three_d = boxes_c.shape[-1] == 7          # [B,N,7] cuboid parameters -> gnms_forward_with_iou3d, [B,N,4] boxes -> ..._iou2d
-        entry, what = (lib.gnms_forward_with_iou3d, "gnms_forward_with_iou3d") if three_d else (lib.gnms_forward_with_iou2d,
-                                                                                                "gnms_forward_with_iou2d")
-        iou = iou_out if iou_out is not None else torch.empty((B, N, N), dtype=torch.float32, device=dev)
-        prob, order, valid, invalid, nvalid, ninvalid = _outputs(B, N, dev, getattr(params, "index_lists", True))
-        nbytes = _workspace_bytes(lib, B, N, params)
-        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-        with on_device(dev):
-            check(entry(ptr(boxes_c), ptr(scores_c), B, N, max(N, 1), ptr(counts), ctypes.byref(params), ptr(iou), ptr(prob), ptr(order),
-                        ptr(valid), ptr(invalid), ptr(nvalid), ptr(ninvalid), ptr(ws), ws.numel(), stream_ptr(dev)), what)
-        ctx.params = params
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(*[x for x in (order, valid, invalid, nvalid, ninvalid, iou) if x is not None])
-        # The masked-group backward (the default) never reads the overlaps, so the matrix is not kept at all.  The unmasked / ungrouped
-        # backward does read it: there it is saved through autograd, whose version counter then catches a caller that overwrites the
-        # (possibly caller-provided) `iou_out` buffer between forward and backward instead of silently producing wrong gradients.
-        # Grouped unmasked 2D: the backward solves its groups from the boxes (gnms_backward_from_boxes: bit-identical overlaps, no matrix reads).
-        # (the forward's own from-boxes gate, alignment included: an unaligned view took the matrix path and keeps the matrix -- ADVICE r4)
-        ctx.bwd_boxes = bool((not three_d) and params.group_boxes and not params.mask_group_boxes and not params.presorted
-                             and boxes_c.data_ptr() % 16 == 0)
-        ctx.reads_iou = not (params.group_boxes and params.mask_group_boxes) and not ctx.bwd_boxes
-        if ctx.bwd_boxes:
-            ctx.save_for_backward(scores_c, counts, ws, boxes_c)
-        elif ctx.reads_iou:
-            ctx.save_for_backward(scores_c, counts, ws, iou)
-        else:
-            ctx.save_for_backward(scores_c, counts, ws)
-        return prob, order, valid, invalid, nvalid, ninvalid, iou
-
-    @staticmethod
-    def backward(ctx, grad_prob, *unused):
-        if grad_prob is None:
-            return None, None, None, None, None
-        lib = _lib.load()
-        if ctx.bwd_boxes:
-            scores_c, counts, ws, boxes_c = ctx.saved_tensors
-            B, N = scores_c.shape
-            dev = scores_c.device
-            grad_prob = grad_prob.contiguous().float()
-            grad_scores = torch.empty_like(scores_c)
-            with on_device(dev):
-                check(lib.gnms_backward_from_boxes(ptr(grad_prob), ptr(boxes_c), ptr(scores_c), B, N, ptr(counts), ctypes.byref(ctx.params),
-                                                   ptr(grad_scores), ptr(ws), ws.numel(), stream_ptr(dev)), "gnms_backward_from_boxes")
-            return grad_scores, None, None, None, None
-        if ctx.reads_iou:
-            scores_c, counts, ws, iou_c = ctx.saved_tensors
-        else:
-            scores_c, counts, ws = ctx.saved_tensors
-            iou_c = scores_c                                   # any valid device pointer: the masked backward does not dereference it
-        B, N = scores_c.shape
-        dev = scores_c.device
-        grad_prob = grad_prob.contiguous().float()
-        grad_scores = torch.empty_like(scores_c)
-        with on_device(dev):
-            check(lib.gnms_backward(ptr(grad_prob), ptr(scores_c), ptr(iou_c), B, N, max(N, 1), ptr(counts), ctypes.byref(ctx.params),
-                                    ptr(grad_scores), None, ptr(ws), ws.numel(), stream_ptr(dev)), "gnms_backward")
-        return grad_scores, None, None, None, None
-
-
-class _GroomedNMSFromBoxesFunction(torch.autograd.Function):
-    """prob = GrooMeD-NMS(scores, boxes) without ever building the N x N overlap matrix (gnms_forward_from_boxes):
-    bit-identical to overlaps.iou_batched + _GroomedNMSFunction, gradient w.r.t. scores (the reference's loss detaches the
-    overlaps, lib/loss/rpn_3d.py:791)."""
-
-    @staticmethod
-    def forward(ctx, scores, boxes, counts, params):
-        lib = _lib.load()
-        B, N = scores.shape
-        dev = scores.device
-        scores_c = scores.contiguous()
-        boxes_c = boxes.contiguous()
-        prob, order, valid, invalid, nvalid, ninvalid = _outputs(B, N, dev, getattr(params, "index_lists", True))
-        nbytes = _workspace_bytes(lib, B, N, params)
-        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-        with on_device(dev):
-            check(lib.gnms_forward_from_boxes(ptr(boxes_c), ptr(scores_c), B, N, ptr(counts), ctypes.byref(params), ptr(prob), ptr(order),
-                                              ptr(valid), ptr(invalid), ptr(nvalid), ptr(ninvalid), ptr(ws), ws.numel(), stream_ptr(dev)),
-                  "gnms_forward_from_boxes")
-        ctx.params = params
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(scores_c, boxes_c, counts, ws)
-        ctx.mark_non_differentiable(*[x for x in (order, valid, invalid, nvalid, ninvalid) if x is not None])
-        return prob, order, valid, invalid, nvalid, ninvalid
-
-    @staticmethod
-    def backward(ctx, grad_prob, *unused):
-        if grad_prob is None:
-            return None, None, None, None
-        lib = _lib.load()
-        scores_c, boxes_c, counts, ws = ctx.saved_tensors
-        B, N = scores_c.shape
-        dev = scores_c.device
-        grad_prob = grad_prob.contiguous().float()
-        grad_scores = torch.empty_like(scores_c)
-        with on_device(dev):
-            check(lib.gnms_backward_from_boxes(ptr(grad_prob), ptr(boxes_c), ptr(scores_c), B, N, ptr(counts), ctypes.byref(ctx.params),
-                                               ptr(grad_scores), ptr(ws), ws.numel(), stream_ptr(dev)), "gnms_backward_from_boxes")
-        return grad_scores, None, None, None
-
-
-# Developer / test switch for the backward of _GroomedNMSBoxGradFunction: "auto" (the library picks: the sparse route for masked groups,
+# Developer / test switch for the backward when `boxes` requires grad: "auto" (the library picks: the sparse route for masked groups,
 # hard sort, unsorted output; the dense route elsewhere) or "dense" (the matrix gradient + gnms_iou2d_backward in every mode).  A call reads
 # it once, in its forward, and its backward takes that route whatever the switch says by then.
 BOX_GRAD_ROUTE = "auto"
 _BOX_ROUTES = {"auto": 0, "dense": 1}
+_NO_BOX_GRAD = -1                                                     # GNMS_BOXES_ROUTE_NONE
+_READS_MATRIX, _READS_BOXES, _BWD_FROM_BOXES, _COPY_BOXES = 1, 2, 4, 8  # GNMS_BWD_* (include/groomed_nms_hip.h)
 
 
-class _GroomedNMSBoxGradFunction(torch.autograd.Function):
-    """The two one-call 2D entries when `boxes` requires grad: the forwards of _GroomedNMSWithIouFunction (with_matrix) and
-    _GroomedNMSFromBoxesFunction, and a backward that also returns dL/dboxes (gnms_backward_boxes) -- what autograd gives
-    the reference for differentiable_nms(scores, iou(boxes, boxes)) when the caller does not detach the overlaps.  The returned
-    matrix of the with-matrix entry stays non-differentiable."""
+class _LayerFunction(torch.autograd.Function):
+    """The layer over ctypes, one node for the four forward entries like `Layer` in csrc/torch_binding.cpp.  mode: which entry runs --
+    _MODE_MATRIX prob = GrooMeD-NMS(scores, iou) (gnms_forward; gradients w.r.t. scores and, only if it requires grad, iou, as autograd gives
+    the reference, lib/groomed_nms.py:111); _MODE_IOU2D / _MODE_IOU3D the overlap matrix of boxes [B,N,4] / cuboids [B,N,7] and the layer on it
+    in one call (a seventh output, non-differentiable as the reference's loss feeds it, lib/loss/rpn_3d.py:791 `.clone().detach()`);
+    _MODE_BOXES the layer from the boxes, no matrix at all.  box_grad: None, or the gnms_backward_boxes route (_BOX_ROUTES) when the 2D boxes
+    require grad -- the backward then returns dL/dboxes too, what autograd gives the reference for
+    differentiable_nms(scores, iou(boxes, boxes)) when the caller does not detach the overlaps.
+    What is kept for the backward, and which backward entry runs, is the library's answer (gnms_backward_reads)."""
 
     @staticmethod
-    def forward(ctx, scores, boxes, counts, params, iou_out, with_matrix):
+    def forward(ctx, scores, src, counts, params, iou_out, mode, box_grad):
         lib = _lib.load()
         B, N = scores.shape
         dev = scores.device
         scores_c = scores.contiguous()
-        boxes_c = boxes.contiguous()
-        aligned = boxes_c.data_ptr() % 16 == 0
-        # (the kernels load a box as one float4; without a box gradient an unaligned view is refused by gnms_iou2d -- here it is copied)
-        boxes_al = boxes_c if aligned else boxes_c.clone()
-        prob, order, valid, invalid, nvalid, ninvalid = _outputs(B, N, dev, getattr(params, "index_lists", True))
-        ws = torch.empty((max(_workspace_bytes(lib, B, N, params), 256),), dtype=torch.uint8, device=dev)
-        iou = None
-        with on_device(dev):
-            if with_matrix:
-                iou = iou_out if iou_out is not None else torch.empty((B, N, N), dtype=torch.float32, device=dev)
-                check(lib.gnms_forward_with_iou2d(ptr(boxes_al), ptr(scores_c), B, N, max(N, 1), ptr(counts), ctypes.byref(params), ptr(iou),
-                                                  ptr(prob), ptr(order), ptr(valid), ptr(invalid), ptr(nvalid), ptr(ninvalid), ptr(ws),
-                                                  ws.numel(), stream_ptr(dev)), "gnms_forward_with_iou2d")
-            else:
-                check(lib.gnms_forward_from_boxes(ptr(boxes_al), ptr(scores_c), B, N, ptr(counts), ctypes.byref(params), ptr(prob), ptr(order),
-                                                  ptr(valid), ptr(invalid), ptr(nvalid), ptr(ninvalid), ptr(ws), ws.numel(), stream_ptr(dev)),
-                      "gnms_forward_from_boxes")
-        ctx.params = params
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(*[x for x in (order, valid, invalid, nvalid, ninvalid, iou) if x is not None])
-        # the matrix is kept (through autograd: its version counter catches a caller that overwrites `iou_out`) only where the backward
-        # will read it: the dense route.  The sparse route recomputes its one overlap per member from the boxes.
-        ctx.route = _BOX_ROUTES[BOX_GRAD_ROUTE]                     # read ONCE per call, here: the backward takes the route the forward planned for
-        sparse = (ctx.route == 0 and params.group_boxes and params.mask_group_boxes and not params.return_sorted_prob
-                  and not params.presorted)                         # (gnms_backward_boxes' own test, nms_layer.hip boxes_sparse_route)
-        ctx.has_iou = iou is not None and not sparse
-        if ctx.has_iou:
-            ctx.save_for_backward(scores_c, boxes_al, counts, ws, iou)
+        route = _NO_BOX_GRAD if box_grad is None else box_grad
+        p = ctypes.byref(params)
+        ld = max(N, 1)
+        boxes = matrix = iou = None           # boxes / matrix: what the forward takes or writes and the backward may read; iou: the matrix as an output
+        if mode == _MODE_MATRIX:
+            matrix, ld = _matrix_layout(src)
         else:
-            ctx.save_for_backward(scores_c, boxes_al, counts, ws)
-        if with_matrix:
-            return prob, order, valid, invalid, nvalid, ninvalid, iou
-        return prob, order, valid, invalid, nvalid, ninvalid
+            boxes = src.contiguous()
+        reads = lib.gnms_backward_reads(mode, p, ptr(boxes), route)
+        if reads < 0:                         # (an empty call has no pointer to ask about, and its backward reads nothing)
+            if scores_c.numel():
+                check(reads, "gnms_backward_reads")
+            reads = 0
+        if reads & _COPY_BOXES:               # the box-gradient kernels load a box as one float4 (without a box gradient the forward
+            boxes = boxes.clone()             # entries refuse an unaligned view themselves)
+        outs = _outputs(B, N, dev, getattr(params, "index_lists", True))
+        ws = torch.empty((max(_workspace_bytes(lib, B, N, params), 256),), dtype=torch.uint8, device=dev)
+        tail = tuple(map(ptr, outs)) + (ptr(ws), ws.numel(), stream_ptr(dev))
+        with on_device(dev):
+            if mode == _MODE_MATRIX:
+                check(lib.gnms_forward(ptr(scores_c), ptr(matrix), B, N, ld, ptr(counts), p, *tail), "gnms_forward")
+            elif mode == _MODE_BOXES:
+                check(lib.gnms_forward_from_boxes(ptr(boxes), ptr(scores_c), B, N, ptr(counts), p, *tail), "gnms_forward_from_boxes")
+            else:
+                matrix = iou = iou_out if iou_out is not None else torch.empty((B, N, N), dtype=torch.float32, device=dev)
+                entry, what = ((lib.gnms_forward_with_iou3d, "gnms_forward_with_iou3d") if mode == _MODE_IOU3D else
+                               (lib.gnms_forward_with_iou2d, "gnms_forward_with_iou2d"))
+                check(entry(ptr(boxes), ptr(scores_c), B, N, ld, ptr(counts), p, ptr(iou), *tail), what)
+        ctx.call = (params, ld, mode, route, reads & _BWD_FROM_BOXES)
+        ctx.set_materialize_grads(False)      # no zero-filled "gradients" for the index outputs
+        if iou is not None:
+            outs += (iou,)
+        ctx.mark_non_differentiable(*[x for x in outs[1:] if x is not None])
+        # A matrix the backward reads is saved through autograd, whose version counter then catches a caller that overwrites the (possibly
+        # caller-provided) `iou_out` buffer between forward and backward instead of silently producing wrong gradients; one it does not
+        # read is not kept at all.
+        ctx.save_for_backward(scores_c, counts, ws, boxes if reads & _READS_BOXES else None, matrix if reads & _READS_MATRIX else None)
+        return outs
 
     @staticmethod
     def backward(ctx, grad_prob, *unused):
         if grad_prob is None:
-            return None, None, None, None, None, None
+            return (None,) * 7
         lib = _lib.load()
-        if ctx.has_iou:
-            scores_c, boxes_al, counts, ws, iou = ctx.saved_tensors
-        else:
-            scores_c, boxes_al, counts, ws = ctx.saved_tensors
-            iou = None
+        scores_c, counts, ws, boxes, matrix = ctx.saved_tensors
         B, N = scores_c.shape
         dev = scores_c.device
+        params, ld, mode, route, from_boxes = ctx.call
+        params = ctypes.byref(params)
         grad_prob = grad_prob.contiguous().float()
         grad_scores = torch.empty_like(scores_c)
-        grad_boxes = torch.empty_like(boxes_al)
-        route = ctx.route
-        ld = max(N, 1)
-        nbytes = lib.gnms_backward_boxes_scratch_bytes(B, N, ld, ctypes.byref(ctx.params), int(iou is not None), route)
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+        grad_src = None
         with on_device(dev):
-            check(lib.gnms_backward_boxes(ptr(grad_prob), ptr(boxes_al), ptr(scores_c), B, N, ptr(counts), ctypes.byref(ctx.params),
-                                          ptr(grad_scores), ptr(grad_boxes), ptr(iou), ld, route, ptr(scratch), nbytes, ptr(ws), ws.numel(),
-                                          stream_ptr(dev)), "gnms_backward_boxes")
-        return grad_scores, grad_boxes, None, None, None, None
+            if route != _NO_BOX_GRAD:
+                grad_src = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
+                nbytes = lib.gnms_backward_boxes_scratch_bytes(B, N, ld, params, int(matrix is not None), route)
+                scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+                check(lib.gnms_backward_boxes(ptr(grad_prob), ptr(boxes), ptr(scores_c), B, N, ptr(counts), params, ptr(grad_scores),
+                                              ptr(grad_src), ptr(matrix), ld, route, ptr(scratch), nbytes, ptr(ws), ws.numel(),
+                                              stream_ptr(dev)), "gnms_backward_boxes")
+            elif from_boxes:
+                check(lib.gnms_backward_from_boxes(ptr(grad_prob), ptr(boxes), ptr(scores_c), B, N, ptr(counts), params, ptr(grad_scores),
+                                                   ptr(ws), ws.numel(), stream_ptr(dev)), "gnms_backward_from_boxes")
+            else:
+                if mode == _MODE_MATRIX and ctx.needs_input_grad[1]:
+                    grad_src = torch.empty((B, N, ld), dtype=torch.float32, device=dev)
+                # (a backward that reads no matrix does not dereference the pointer: any valid device pointer will do)
+                check(lib.gnms_backward(ptr(grad_prob), ptr(scores_c), ptr(matrix if matrix is not None else scores_c), B, N, ld, ptr(counts),
+                                        params, ptr(grad_scores), ptr(grad_src), ptr(ws), ws.numel(), stream_ptr(dev)), "gnms_backward")
+                if grad_src is not None and ld != N:
+                    grad_src = grad_src[:, :, :N]
+        return grad_scores, grad_src, None, None, None, None, None
 
 
 class _SoftSortFunction(torch.autograd.Function):
@@ -485,7 +347,7 @@ def differentiable_nms_batched(scores, iou, counts=None, nms_threshold=0.4, prun
     ext = _binding()
     if ext and scores.is_cuda:
         return tuple(_layer(ext, scores.float(), iou.float(), counts, None, _MODE_MATRIX, params)[:6])
-    return _GroomedNMSFunction.apply(scores.float(), iou.float(), counts, params)
+    return _LayerFunction.apply(scores.float(), iou.float(), counts, params, None, _MODE_MATRIX, None)
 
 
 def differentiable_nms_with_iou2d_batched(scores, boxes, counts=None, iou_out=None, nms_threshold=0.4, pruning_method="linear",
@@ -499,11 +361,11 @@ def differentiable_nms_with_iou2d_batched(scores, boxes, counts=None, iou_out=No
     if counts is not None:
         counts = counts.to(device=scores.device, dtype=torch.int32).contiguous()
     if boxes.requires_grad and torch.is_grad_enabled():              # dL/dboxes as well; without it the calls below, unchanged
-        return _GroomedNMSBoxGradFunction.apply(scores.float(), boxes.float(), counts, params, iou_out, True)
+        return _LayerFunction.apply(scores.float(), boxes.float(), counts, params, iou_out, _MODE_IOU2D, _BOX_ROUTES[BOX_GRAD_ROUTE])
     ext = _binding()
     if ext and scores.is_cuda:
         return tuple(_layer(ext, scores.float(), boxes.float(), counts, iou_out, _MODE_IOU2D, params))
-    return _GroomedNMSWithIouFunction.apply(scores.float(), boxes.float(), counts, params, iou_out)
+    return _LayerFunction.apply(scores.float(), boxes.float(), counts, params, iou_out, _MODE_IOU2D, None)
 
 
 def differentiable_nms_with_iou3d_batched(scores, params3d, counts=None, iou_out=None, nms_threshold=0.4, pruning_method="linear",
@@ -521,7 +383,7 @@ def differentiable_nms_with_iou3d_batched(scores, params3d, counts=None, iou_out
     ext = _binding()
     if ext and scores.is_cuda:
         return tuple(_layer(ext, scores.float(), params3d.float(), counts, iou_out, _MODE_IOU3D, params))
-    return _GroomedNMSWithIouFunction.apply(scores.float(), params3d.float(), counts, params, iou_out)
+    return _LayerFunction.apply(scores.float(), params3d.float(), counts, params, iou_out, _MODE_IOU3D, None)
 
 
 def differentiable_nms_from_boxes_batched(scores, boxes, counts=None, nms_threshold=0.4, pruning_method="linear", temperature=0.01,
@@ -535,11 +397,11 @@ def differentiable_nms_from_boxes_batched(scores, boxes, counts=None, nms_thresh
     if counts is not None:
         counts = counts.to(device=scores.device, dtype=torch.int32).contiguous()
     if boxes.requires_grad and torch.is_grad_enabled():              # dL/dboxes as well; without it the calls below, unchanged
-        return _GroomedNMSBoxGradFunction.apply(scores.float(), boxes.float(), counts, params, None, False)
+        return _LayerFunction.apply(scores.float(), boxes.float(), counts, params, None, _MODE_BOXES, _BOX_ROUTES[BOX_GRAD_ROUTE])
     ext = _binding()
     if ext and scores.is_cuda:
         return tuple(_layer(ext, scores.float(), boxes.float(), counts, None, _MODE_BOXES, params)[:6])
-    return _GroomedNMSFromBoxesFunction.apply(scores.float(), boxes.float(), counts, params)
+    return _LayerFunction.apply(scores.float(), boxes.float(), counts, params, None, _MODE_BOXES, None)
 
 
 def differentiable_nms(scores_unsorted, iou_unsorted, nms_threshold=0.4, pruning_method="linear", temperature=0.01,

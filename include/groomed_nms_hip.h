@@ -266,6 +266,43 @@ int gnms_backward_boxes(const float* grad_prob, const float* boxes, const float*
                         const gnms_params* params, float* grad_scores, float* grad_boxes, const float* iou, int64_t ld, int route,
                         void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* What the backward of a forward call will read besides scores / counts / workspace -- the ONE place a binding learns what to keep alive
+ * between the two calls and which gnms_backward* entry follows.  Pure host code: no HIP call, no launch, no device needed.  It answers
+ * from the same gate definitions the entries themselves branch on (nms_layer.hip).
+ *   entry           the forward entry, GNMS_ENTRY_*
+ *   boxes           the pointer that entry gets as boxes / params3d (only its 16-byte alignment is looked at); NULL for GNMS_ENTRY_MATRIX
+ *   box_grad_route  GNMS_BOXES_ROUTE_NONE: gnms_backward, or with GNMS_BWD_FROM_BOXES gnms_backward_from_boxes, follows;
+ *                   GNMS_BOXES_ROUTE_AUTO / _DENSE: gnms_backward_boxes follows with that route (the two 2D one-call entries only)
+ * Returns GNMS_BWD_* flags (>= 0), or a negative gnms status with gnms_last_error set (unknown entry / route, NULL params, NULL boxes
+ * where the entry takes some).  `masked` = group_boxes && mask_group_boxes; `default` = masked && !return_sorted_prob && !presorted:
+ *
+ *   no box gradient      mode                                                      flags
+ *   ENTRY_MATRIX         every mode                                                READS_MATRIX  (the caller's own tensor; masked groups read
+ *                                                                                                 it only for grad_iou, and keeping it costs nothing)
+ *   ENTRY_WITH_IOU2D     masked                                                    0             (the matrix is free to be overwritten at once)
+ *                        group_boxes, unmasked, !presorted, boxes 16-byte aligned  READS_BOXES | FROM_BOXES  (the forward ran from the boxes too)
+ *                        everything else (ungrouped; presorted; an unaligned view) READS_MATRIX  (the forward itself refuses an unaligned view
+ *                                                                                                 as things stand: its gnms_iou2d does)
+ *   ENTRY_WITH_IOU3D     masked                                                    0
+ *                        everything else                                           READS_MATRIX
+ *   ENTRY_FROM_BOXES     every mode it accepts                                     READS_BOXES | FROM_BOXES
+ *
+ *   box gradient         route AUTO and default mode (the sparse route)            READS_BOXES
+ *                        route DENSE, or any other mode                            READS_BOXES | READS_MATRIX  (pass the forward's matrix as `iou`
+ *                                                                                                 where the entry wrote one, else NULL)
+ *                        + boxes not 16-byte aligned                               | COPY_BOXES
+ */
+#define GNMS_ENTRY_MATRIX 0     /* gnms_forward */
+#define GNMS_ENTRY_WITH_IOU2D 1 /* gnms_forward_with_iou2d */
+#define GNMS_ENTRY_WITH_IOU3D 2 /* gnms_forward_with_iou3d */
+#define GNMS_ENTRY_FROM_BOXES 3 /* gnms_forward_from_boxes */
+#define GNMS_BOXES_ROUTE_NONE -1
+#define GNMS_BWD_READS_MATRIX 1 /* the backward reads the overlap matrix the forward read or wrote */
+#define GNMS_BWD_READS_BOXES 2  /* the backward reads the boxes */
+#define GNMS_BWD_FROM_BOXES 4   /* the backward entry is gnms_backward_from_boxes */
+#define GNMS_BWD_COPY_BOXES 8   /* gnms_backward_boxes and the forward in front of it load a box as one float4: give BOTH a 16-byte aligned copy */
+int gnms_backward_reads(int entry, const gnms_params* params, const void* boxes, int box_grad_route);
+
 /* profiling hook: re-runs only the threshold bit-matrix kernel (the single full read of the overlap matrix, the
  * dominant kernel of gnms_forward) on a workspace a previous gnms_forward call filled. */
 int gnms_profile_bitmask(const float* iou, int B, int N, int64_t ld, const int32_t* counts, float nms_threshold,

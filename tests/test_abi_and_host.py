@@ -91,6 +91,50 @@ def test_argument_validation_without_gpu(lib):
         pruning_function(torch.rand(3, 3), pruning_method="bogus")
 
 
+def test_backward_reads_table(lib):
+    """gnms_backward_reads (host code only) against a table written out here: what the backward of each forward entry reads in each mode.
+    The expected values were read off the three predicates the bindings and the library carried before this entry existed (the with-iou2d
+    from-boxes gate, the 3D from-records gate, the masked-default predicate of gnms_backward / gnms_backward_boxes); only the flag values
+    are shared with the product."""
+    from groomed_nms_amd._lib import GnmsParams
+    MATRIX_IN, WITH2D, WITH3D, FROM_BOXES = 0, 1, 2, 3
+    M, BX, FB, COPY = 1, 2, 4, 8                                     # READS_MATRIX, READS_BOXES, FROM_BOXES, COPY_BOXES
+    NONE, AUTO, DENSE = -1, 0, 1
+    al, un = ctypes.c_void_p(4096), ctypes.c_void_p(4096 + 4)        # never dereferenced: only the alignment is looked at
+
+    def P(group=1, mask=1, sorted_prob=0, presorted=0):
+        p = GnmsParams()
+        lib.gnms_default_params(ctypes.byref(p))
+        p.group_boxes, p.mask_group_boxes, p.return_sorted_prob, p.presorted = group, mask, sorted_prob, presorted
+        return p
+
+    table = [
+        # entry, params, boxes, route -> flags
+        (MATRIX_IN, P(), None, NONE, M), (MATRIX_IN, P(mask=0), None, NONE, M), (MATRIX_IN, P(group=0), None, NONE, M),
+        (MATRIX_IN, P(presorted=1), al, NONE, M),
+        (WITH2D, P(), al, NONE, 0), (WITH2D, P(), un, NONE, 0), (WITH2D, P(sorted_prob=1), al, NONE, 0), (WITH2D, P(presorted=1), al, NONE, 0),
+        (WITH2D, P(mask=0), al, NONE, BX | FB), (WITH2D, P(mask=0, sorted_prob=1), al, NONE, BX | FB),
+        (WITH2D, P(mask=0), un, NONE, M), (WITH2D, P(mask=0, presorted=1), al, NONE, M),
+        (WITH2D, P(group=0), al, NONE, M), (WITH2D, P(group=0, mask=0), al, NONE, M), (WITH2D, P(group=0), un, NONE, M),
+        (WITH3D, P(), al, NONE, 0), (WITH3D, P(), un, NONE, 0), (WITH3D, P(presorted=1), al, NONE, 0),
+        (WITH3D, P(mask=0), al, NONE, M), (WITH3D, P(group=0), al, NONE, M), (WITH3D, P(group=0, mask=0), un, NONE, M),
+        (FROM_BOXES, P(), al, NONE, BX | FB), (FROM_BOXES, P(mask=0), al, NONE, BX | FB), (FROM_BOXES, P(sorted_prob=1), al, NONE, BX | FB),
+        (WITH2D, P(), al, AUTO, BX), (FROM_BOXES, P(), al, AUTO, BX), (WITH2D, P(), un, AUTO, BX | COPY),
+        (WITH2D, P(sorted_prob=1), al, AUTO, BX | M), (WITH2D, P(mask=0), al, AUTO, BX | M), (WITH2D, P(group=0), al, AUTO, BX | M),
+        (WITH2D, P(presorted=1), al, AUTO, BX | M), (FROM_BOXES, P(mask=0), al, AUTO, BX | M), (FROM_BOXES, P(mask=0), un, AUTO, BX | M | COPY),
+        (WITH2D, P(), al, DENSE, BX | M), (WITH2D, P(mask=0), al, DENSE, BX | M), (WITH2D, P(group=0), al, DENSE, BX | M),
+        (WITH2D, P(sorted_prob=1), al, DENSE, BX | M), (FROM_BOXES, P(), al, DENSE, BX | M), (FROM_BOXES, P(), un, DENSE, BX | M | COPY),
+    ]
+    for entry, p, boxes, route, want in table:
+        got = lib.gnms_backward_reads(entry, ctypes.byref(p), boxes, route)
+        assert got == want, (entry, (p.group_boxes, p.mask_group_boxes, p.return_sorted_prob, p.presorted), boxes.value if boxes else None, route, got, want)
+    p = P()
+    for bad in ((-1, ctypes.byref(p), al, NONE), (4, ctypes.byref(p), al, NONE), (WITH2D, None, al, NONE), (WITH2D, ctypes.byref(p), None, NONE),
+                (WITH3D, ctypes.byref(p), None, NONE), (FROM_BOXES, ctypes.byref(p), None, NONE), (FROM_BOXES, ctypes.byref(p), None, AUTO),
+                (WITH2D, ctypes.byref(p), al, 2), (MATRIX_IN, ctypes.byref(p), al, AUTO), (WITH3D, ctypes.byref(p), al, DENSE)):
+        assert lib.gnms_backward_reads(*bad) == -1 and b"gnms_backward_reads" in lib.gnms_last_error(), bad[0::2]
+
+
 def test_product_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip("a GPU is present")

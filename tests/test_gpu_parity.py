@@ -585,9 +585,9 @@ def test_from_boxes_path_is_bit_identical(G):
             assert torch.equal(s1.grad, s2.grad), (B, N, kw)
     with pytest.raises(GnmsError):
         import ctypes
-        from groomed_nms_amd.groomed_nms import _params, _GroomedNMSFromBoxesFunction
-        _GroomedNMSFromBoxesFunction.apply(torch.rand((1, 8), device="cuda"), torch.rand((1, 8, 4), device="cuda"), None,
-                                           _params(0.4, "linear", 0.01, 0.3, False, False, True, 100))     # ungrouped needs the matrix
+        from groomed_nms_amd.groomed_nms import _params, _LayerFunction, _MODE_BOXES
+        _LayerFunction.apply(torch.rand((1, 8), device="cuda"), torch.rand((1, 8, 4), device="cuda"), None,
+                             _params(0.4, "linear", 0.01, 0.3, False, False, True, 100), None, _MODE_BOXES, None)     # ungrouped needs the matrix
 
 
 def test_capturable_in_a_hip_graph(G):
@@ -1779,7 +1779,9 @@ def test_float64_numpy_call_site(G, golden_f64site):
 def test_ctypes_binding_still_serves_the_layer():
     """The layer's default host path is the C++ binding (gnms_torch); the ctypes + torch.autograd.Function path over the same C ABI is
     the fallback (GNMS_BINDING=ctypes).  Both must give the oracle's results: a child process runs the four batched entries through
-    ctypes -- forward, index lists, backward -- and compares them bit for bit with what this process gets through the binding."""
+    ctypes -- forward, index lists, backward -- and compares them bit for bit with what this process gets through the binding.
+    The B = 2, N = 200 cases are about what each binding keeps for the backward and which backward entry it calls (both ask
+    gnms_backward_reads): from the boxes, from the kept matrix (2D ungrouped, 3D unmasked), and a box view at data_ptr() % 16 == 4."""
     import os, subprocess, sys, tempfile
     from groomed_nms_amd import synthetic, groomed_nms as GN, overlaps
     assert GN._binding(), "the C++ binding is not in use in this process"
@@ -1802,6 +1804,21 @@ run("boxes", GN.differentiable_nms_from_boxes_batched, s, bt)
 run("matrix", GN.differentiable_nms_batched, s, overlaps.iou_batched(bt))
 run("unmasked", GN.differentiable_nms_batched, s, overlaps.iou_batched(bt), mask_group_boxes=False)
 run("with3d", GN.differentiable_nms_with_iou3d_batched, s3, torch.from_numpy(p3).cuda())
+# what each binding keeps for the backward, and the backward entry it then calls (gnms_backward_reads)
+b2, s2 = synthetic.batch_2d(79, 2, 200, "clustered", per=20)
+p2, s4 = synthetic.batch_3d(80, 2, 200, clustered=True, per=20)
+cnt = torch.tensor([200, 137], dtype=torch.int32).cuda()
+bt2 = torch.from_numpy(b2).cuda()
+off = torch.empty((2 * 200 * 4 + 4,), device="cuda")[1:1601].view(2, 200, 4).copy_(bt2)      # a view one float into a larger buffer
+assert off.data_ptr() % 16 == 4 and off.is_contiguous()
+run("with2d_boxes_bwd", GN.differentiable_nms_with_iou2d_batched, s2, bt2, counts=cnt, mask_group_boxes=False)
+run("with2d_matrix_bwd", GN.differentiable_nms_with_iou2d_batched, s2, bt2, counts=cnt, group_boxes=False)
+try:
+    run("with2d_unaligned", GN.differentiable_nms_with_iou2d_batched, s2, off, counts=cnt, mask_group_boxes=False)
+    out["with2d_unaligned/error"] = np.array("")
+except GN._lib.GnmsError as e:
+    out["with2d_unaligned/error"] = np.array(str(e))
+run("with3d_unmasked", GN.differentiable_nms_with_iou3d_batched, s4, torch.from_numpy(p2).cuda(), counts=cnt, mask_group_boxes=False)
 np.savez(sys.argv[1], **out)
 """
     with tempfile.TemporaryDirectory() as d:
@@ -1825,6 +1842,24 @@ np.savez(sys.argv[1], **out)
         run("matrix", GN.differentiable_nms_batched, s, overlaps.iou_batched(bt))
         run("unmasked", GN.differentiable_nms_batched, s, overlaps.iou_batched(bt), mask_group_boxes=False)
         run("with3d", GN.differentiable_nms_with_iou3d_batched, s3, torch.from_numpy(p3).cuda())
+        b2, s2 = synthetic.batch_2d(79, 2, 200, "clustered", per=20)
+        p2, s4 = synthetic.batch_3d(80, 2, 200, clustered=True, per=20)
+        cnt = torch.tensor([200, 137], dtype=torch.int32).cuda()
+        bt2 = torch.from_numpy(b2).cuda()
+        off = torch.empty((2 * 200 * 4 + 4,), device="cuda")[1:1601].view(2, 200, 4).copy_(bt2)
+        assert off.data_ptr() % 16 == 4 and off.is_contiguous()
+        run("with2d_boxes_bwd", GN.differentiable_nms_with_iou2d_batched, s2, bt2, counts=cnt, mask_group_boxes=False)
+        run("with2d_matrix_bwd", GN.differentiable_nms_with_iou2d_batched, s2, bt2, counts=cnt, group_boxes=False)
+        # the unaligned view: gnms_forward_with_iou2d does not run from the boxes, and the matrix path's gnms_iou2d refuses such a pointer -- in
+        # both bindings alike, before anything is kept or any backward runs on it (with a forward that accepted the view, the four
+        # comparisons of run() would apply as they stand)
+        if str(ref["with2d_unaligned/error"]):
+            with pytest.raises(GN._lib.GnmsError) as err:
+                run("with2d_unaligned", GN.differentiable_nms_with_iou2d_batched, s2, off, counts=cnt, mask_group_boxes=False)
+            assert "16-byte aligned" in str(err.value) and str(ref["with2d_unaligned/error"]) in str(err.value)     # (the binding's starts "GNMS: ")
+        else:
+            run("with2d_unaligned", GN.differentiable_nms_with_iou2d_batched, s2, off, counts=cnt, mask_group_boxes=False)
+        run("with3d_unmasked", GN.differentiable_nms_with_iou3d_batched, s4, torch.from_numpy(p2).cuda(), counts=cnt, mask_group_boxes=False)
 
 
 def test_n_rank_launcher_end_to_end():
