@@ -36,6 +36,9 @@ _SIGNATURES = {
     "gnms_iou2d_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "gnms_iou2d_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, c_vp, c_vp,
                                            ctypes.c_size_t, c_vp]),
+    "gnms_iou3d_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "gnms_iou3d_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_vp, c_vp,
+                                           c_vp, ctypes.c_size_t, c_vp]),
     "gnms_corners_of_cuboid": (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, c_vp]),
     "gnms_iou2d_f64": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int64, c_vp]),
     "gnms_corners_of_cuboid_f64": (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int, c_vp, c_vp]),
@@ -71,6 +74,11 @@ _SIGNATURES = {
     "gnms_backward_boxes": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.POINTER(GnmsParams), c_vp, c_vp, c_vp,
                                            ctypes.c_int64, ctypes.c_int, c_vp, ctypes.c_size_t, c_vp, ctypes.c_size_t, c_vp]),
     "gnms_backward_reads": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GnmsParams), c_vp, ctypes.c_int]),
+    "gnms_backward_cuboids_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(GnmsParams), ctypes.c_int,
+                                                              ctypes.c_int]),
+    "gnms_backward_cuboids": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.POINTER(GnmsParams), c_vp, c_vp, c_vp,
+                                             ctypes.c_int64, ctypes.c_int, c_vp, ctypes.c_size_t, c_vp, ctypes.c_size_t, c_vp]),
+    "gnms_backward_cuboids_reads": (ctypes.c_int, [ctypes.POINTER(GnmsParams), c_vp, ctypes.c_int]),
     "gnms_profile_bitmask": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, ctypes.c_float, c_vp,
                                             ctypes.c_size_t, c_vp]),
     "gnms_profile_bitmask_boxes": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_float, c_vp, ctypes.c_size_t, c_vp]),

@@ -11,7 +11,7 @@ OUT = os.path.join(HERE, "libgroomed_nms_hip.so")
 # Longest compile first (LABNOTES R15): the jobs start in this order, so the NMS layer's units -- 15 to 30 s each, everything else under 6 s -- go
 # ahead of the small sources and a clean build takes about as long as the slowest of them.
 SOURCES = ["nms_layer.hip", "nms_tail_write_records.hip", "nms_tail_write_boxes.hip", "nms_tail_boxes.hip", "nms_tail_matrix.hip", "nms_tail_records.hip",
-           "soft_sort.hip", "aploss.hip", "iou_kernels.hip", "classic_nms.hip", "nms_profile.hip", "nms_others.hip", "proposals.hip", "host_mailbox.hip", "iou3d_exact.hip", "targets.hip", "detect3d.hip", "kitti_eval.hip", "kitti_rows.hip", "sampling.hip", "regression.hip", "after_nms.hip", "heads.hip", "loss.hip", "bbox_stats.hip", "preprocess.hip", "optim.hip", "iou_backward.hip"]
+           "soft_sort.hip", "aploss.hip", "iou_kernels.hip", "classic_nms.hip", "nms_profile.hip", "nms_others.hip", "proposals.hip", "host_mailbox.hip", "iou3d_exact.hip", "targets.hip", "detect3d.hip", "kitti_eval.hip", "kitti_rows.hip", "sampling.hip", "regression.hip", "after_nms.hip", "heads.hip", "loss.hip", "bbox_stats.hip", "preprocess.hip", "optim.hip", "iou_backward.hip", "iou3d_backward.hip"]
 # -ffp-contract=off: products and sums round separately, like the reference's torch CPU kernels
 # (lib/core.py:499-508) -- this is what makes the overlap matrices bit-identical.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",

@@ -152,9 +152,9 @@ __device__ __forceinline__ float nms_overlap3d_guarded1(const Row& a, const Col1
 // matrix write instead of after it).  Same operations in the same order as nms_overlap3d / nms_overlap3d_exact, one column wide:
 // with -ffp-contract=off every product, sum, division and the v_rcp_f32 round exactly as there, and v_min/v_max do not depend on
 // which operand sits in an SGPR, so the result equals the matrix entry bit for bit (tests/test_gpu_parity.py compares the paths).
-__device__ __forceinline__ float nms_overlap3d_pair(const float* __restrict__ ra, const float* __restrict__ rb, float thr) {
-    const float4 au = reinterpret_cast<const float4*>(ra)[0], av = reinterpret_cast<const float4*>(ra)[1], ae = reinterpret_cast<const float4*>(ra)[2];
-    const float4 bu = reinterpret_cast<const float4*>(rb)[0], bv = reinterpret_cast<const float4*>(rb)[1], be = reinterpret_cast<const float4*>(rb)[2];
+// (the record of either box as its three float4: u | v | e)
+__device__ __forceinline__ float nms_overlap3d_pair(const float4 au, const float4 av, const float4 ae, const float4 bu, const float4 bv, const float4 be,
+                                                    float thr) {
     const float dx = fminf(av.x, bv.x) - fmaxf(au.w, bu.w);
     const float dy = fminf(au.z, bu.z) - fmaxf(au.y, bu.y);
     const float dz = fminf(av.z, bv.z) - fmaxf(av.y, bv.y);
@@ -176,6 +176,11 @@ __device__ __forceinline__ float nms_overlap3d_pair(const float* __restrict__ ra
         q = 0.5f * (1.0f + g);
     }
     return q;
+}
+__device__ __forceinline__ float nms_overlap3d_pair(const float* __restrict__ ra, const float* __restrict__ rb, float thr) {
+    const float4* a = reinterpret_cast<const float4*>(ra);
+    const float4* b = reinterpret_cast<const float4*>(rb);
+    return nms_overlap3d_pair(a[0], a[1], a[2], b[0], b[1], b[2], thr);
 }
 
 }  // namespace gnms_iou3d

@@ -43,22 +43,7 @@ __global__ __launch_bounds__(kWavesPerWG * 64) void iou2d_kernel(const float* __
 // ------------------------------------------------------------------------------------------------
 using gnms_iou3d::kRec;
 
-__device__ __forceinline__ void aabb_record(const float (&cx)[8], const float (&cy)[8], const float (&cz)[8], float* rec) {
-    float mnx = cx[0], mxx = cx[0], mny = cy[0], mxy = cy[0], mnz = cz[0], mxz = cz[0];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-        mnx = fminf(mnx, cx[k]); mxx = fmaxf(mxx, cx[k]);
-        mny = fminf(mny, cy[k]); mxy = fmaxf(mxy, cy[k]);
-        mnz = fminf(mnz, cz[k]); mxz = fmaxf(mxz, cz[k]);
-    }
-    float vol = ((mxx - mnx) * (mxy - mny)) * (mxz - mnz);
-    float x0 = fminf(fminf(cx[2], cx[3]), fminf(cx[6], cx[7])), x1 = fmaxf(fmaxf(cx[2], cx[3]), fmaxf(cx[6], cx[7]));
-    float z0 = fminf(fminf(cz[2], cz[3]), fminf(cz[6], cz[7])), z1 = fmaxf(fmaxf(cz[2], cz[3]), fmaxf(cz[6], cz[7]));
-    rec[0] = vol; rec[1] = mny; rec[2] = mxy; rec[3] = x0; rec[4] = x1; rec[5] = z0; rec[6] = z1;
-    rec[7] = (x1 - x0) * (z1 - z0);
-    rec[8] = x1 - x0; rec[9] = mxy - mny; rec[10] = z1 - z0;                      // extents, used by the fast NMS-overlap kernel
-    rec[11] = gnms_iou3d::record_bad_flag(x0, x1, mny, mxy, z0, z1, rec[8], rec[9], rec[10]);   // 0 = sane (iou3d_pair.h)
-}
+using gnms_geom::aabb_record;   // cuboid_corners.h (shared with the 3D overlap backward)
 
 
 __global__ void aabb_from_corners_kernel(const float* __restrict__ corners, long count, float* __restrict__ rec) {

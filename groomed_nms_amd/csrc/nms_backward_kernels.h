@@ -12,6 +12,7 @@
 #pragma once
 #include "nms_kernels.h"
 #include "iou_grad.h"
+#include "iou3d_grad.h"
 
 namespace gnms {
 
@@ -303,6 +304,96 @@ __global__ __launch_bounds__(256) void bwd_masked_boxes_kernel(const float* __re
         add_box_grad(a, hb, p, bwd_member_cotangent(gp, I, k, h, p, P), acc);
     }
     gb[ck] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+}
+
+// dL/dparams3d of the masked-group layer behind gnms_forward_with_iou3d: bwd_masked_boxes_kernel for cuboids.  The same two
+// kinds of workgroups and the same order of the sums; a box's record is rebuilt from its seven parameters (the forward's floats:
+// corners_of + aabb_record), the matrix entry q of (member, head) is the forward's own definition (nms_overlap3d_pair, guard band
+// included), the pair arithmetic is iou3d_grad.h's with the member as the row box, exactly as gnms_iou3d_backward<method 2> evaluates
+// the same entry.  Six extent sums per box, carried to the seven parameters ONCE per box (params_grad).
+struct CuboidRec {
+    float4 u, v, e;
+};
+__device__ __forceinline__ CuboidRec cuboid_rec(const float* __restrict__ p) {
+    CuboidRec r;
+    gnms_iou3d_grad::record_of_params(p, r.u, r.v, r.e);
+    return r;
+}
+__device__ __forceinline__ float bwd_member_cotangent3d(const float* __restrict__ gp, const ImgPtrs& I, int k, int h, const CuboidRec& member,
+                                                        const CuboidRec& head, const gnms_params& P) {
+    const float q = gnms_iou3d::nms_overlap3d_pair(member.u, member.v, member.e, head.u, head.v, head.e, P.nms_threshold);
+    const float d = gnms_prune_grad(q, P.nms_threshold, P.temperature, P.pruning_method);
+    return (-(bwd_gx_of(gp, I, k) * I.sscore[h])) * d;
+}
+__device__ __forceinline__ void store_params_grad(const float* __restrict__ p, const float (&G)[6], float* __restrict__ out) {
+    float d[7];
+    gnms_iou3d_grad::params_grad(p, G, d);
+#pragma unroll
+    for (int c = 0; c < 7; ++c) out[c] = d[c];
+}
+
+__global__ __launch_bounds__(256) void bwd_masked_cuboids_kernel(const float* __restrict__ grad_prob, const float* __restrict__ params3d, int N,
+                                                                 const int* __restrict__ counts, gnms_params P, char* ws, gnms_ws_layout L,
+                                                                 float* __restrict__ grad_params, int elem_blocks) {
+    using namespace gnms_iou3d_grad;
+    const int b = blockIdx.y;
+    const int n = gnms_count(counts, b, N);
+    ImgPtrs I = img_ptrs(ws, L, b);
+    const float* px = params3d + (size_t)b * N * 7;
+    float* gb = grad_params + (size_t)b * N * 7;
+    const float* gp = grad_prob + (size_t)b * N;
+    const unsigned last = (unsigned)(n > 0 ? n - 1 : 0);
+    if ((int)blockIdx.x >= elem_blocks) {
+        if (n == 0) return;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int nheads = min(I.misc[1], n);
+        const int nhb = (int)gridDim.x - elem_blocks;
+        for (int hi = ((int)blockIdx.x - elem_blocks) * 4 + wave; hi < nheads; hi += nhb * 4) {
+            const int k = (int)min((unsigned)I.hlist[hi], last);
+            const int hstart = I.gstart[k], hlen = I.glen[k];
+            if (hstart < 0 || hlen < 2 || hstart + hlen > n) continue;                    // (a workspace the forward never filled)
+            const int ck = (int)min((unsigned)I.order[k], last);
+            const CuboidRec hr = cuboid_rec(px + (size_t)ck * 7);
+            const Rec hb = rec_of(hr.u, hr.v);
+            float acc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            for (int base = 1; base < hlen; base += 64) {
+                const int t = base + lane;
+                float term[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                if (t < hlen) {
+                    const int mk = (int)min((unsigned)I.gsorted[hstart + t], last);
+                    const CuboidRec mr = cuboid_rec(px + (size_t)min((unsigned)I.order[mk], last) * 7);
+                    const Rec a = rec_of(mr.u, mr.v);
+                    const Pair p = pair_of(a, hb);
+                    add_extent_grad<2>(hb, a, p, bwd_member_cotangent3d(gp, I, mk, k, mr, hr, P), term);
+                }
+                const int cnt = min(64, hlen - base);
+                for (int u = 0; u < cnt; ++u) {
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) acc[c] += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(term[c]), u));
+                }
+            }
+            if (lane == 0) store_params_grad(px + (size_t)ck * 7, acc, gb + (size_t)ck * 7);
+        }
+        return;
+    }
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= N) return;
+    if (k >= n) {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) gb[(size_t)k * 7 + c] = 0.0f;
+        return;
+    }
+    const int ck = (int)min((unsigned)I.order[k], last);
+    const int h = I.head[k];
+    if (h == k && I.glen[k] > 1 && I.misc[1] > 0) return;            // written by the head waves (hlist holds exactly these)
+    float acc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (h >= 0 && h != k && h < n) {
+        const CuboidRec mr = cuboid_rec(px + (size_t)ck * 7), hr = cuboid_rec(px + (size_t)min((unsigned)I.order[h], last) * 7);
+        const Rec a = rec_of(mr.u, mr.v), hb = rec_of(hr.u, hr.v);
+        const Pair p = pair_of(a, hb);
+        add_extent_grad<2>(a, hb, p, bwd_member_cotangent3d(gp, I, k, h, mr, hr, P), acc);
+    }
+    store_params_grad(px + (size_t)ck * 7, acc, gb + (size_t)ck * 7);
 }
 
 }  // namespace gnms

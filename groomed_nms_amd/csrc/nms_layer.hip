@@ -1347,6 +1347,69 @@ extern "C" int gnms_backward_boxes(const float* grad_prob, const float* boxes, c
 }
 
 // ------------------------------------------------------------------------------------------------
+// backward with the gradient w.r.t. the cuboids: gnms_backward_boxes for gnms_forward_with_iou3d
+// ------------------------------------------------------------------------------------------------
+namespace {
+BoxesScratch cuboids_scratch(int B, int N, int64_t ld, bool have_overlap) {
+    BoxesScratch s;
+    s.grad_iou = gnms_align_up(sizeof(float) * (size_t)B * N * ld, 256);
+    s.iou = have_overlap ? 0 : s.grad_iou;
+    s.reduce = gnms_iou3d_backward_workspace_bytes(B, N, N);
+    s.total = s.grad_iou + s.iou + s.reduce;
+    return s;
+}
+}  // namespace
+
+// host code only (the table stands in include/groomed_nms_hip.h); the same gate as gnms_backward_cuboids branches on
+extern "C" int gnms_backward_cuboids_reads(const gnms_params* params, const void* params3d, int route) {
+    GNMS_CHECK_ARG(params != nullptr, "gnms_backward_cuboids_reads: params is NULL");
+    GNMS_CHECK_ARG(params3d != nullptr, "gnms_backward_cuboids_reads: params3d is NULL");
+    GNMS_CHECK_ARG(route == GNMS_BOXES_ROUTE_AUTO || route == GNMS_BOXES_ROUTE_DENSE, "gnms_backward_cuboids_reads: unknown route %d", route);
+    return GNMS_BWD_READS_BOXES | (boxes_sparse_route(*params, route) ? 0 : GNMS_BWD_READS_MATRIX);
+}
+
+extern "C" size_t gnms_backward_cuboids_scratch_bytes(int B, int N, int64_t ld, const gnms_params* params, int have_overlap, int route) {
+    if (!params || B <= 0 || N <= 0 || ld < N || boxes_sparse_route(*params, route)) return 0;
+    return cuboids_scratch(B, N, ld, have_overlap != 0).total;
+}
+
+extern "C" int gnms_backward_cuboids(const float* grad_prob, const float* params3d, const float* scores, int B, int N, const int32_t* counts,
+                                     const gnms_params* params, float* grad_scores, float* grad_params3d, const float* overlap, int64_t ld,
+                                     int route, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    LayerCall c;
+    GNMS_CHECK_ARG(route == GNMS_BOXES_ROUTE_AUTO || route == GNMS_BOXES_ROUTE_DENSE, "gnms_backward_cuboids: unknown route %d", route);
+    GNMS_BEGIN_CALL("gnms_backward_cuboids", &c, B, N, ld, counts, params, workspace, workspace_bytes, stream, false,
+                    grad_prob && params3d && scores && grad_scores && grad_params3d, "gnms_backward_cuboids: null pointer");
+    if (boxes_sparse_route(c.P, route)) {
+        // (the masked backward never dereferences the matrix pointer when no matrix gradient is asked for)
+        const int rc = gnms_backward(grad_prob, scores, params3d, B, N, N, counts, params, grad_scores, nullptr, workspace, workspace_bytes, stream);
+        if (rc) return rc;
+        const int elem_blocks = gnms_div_up(N, 256), head_blocks = N >= 2048 ? 128 : gnms_div_up(N, 16);
+        bwd_masked_cuboids_kernel<<<dim3(elem_blocks + head_blocks, B), 256, 0, c.st>>>(grad_prob, params3d, N, counts, c.P, c.ws, c.L, grad_params3d,
+                                                                                        elem_blocks);
+        GNMS_CHECK_LAUNCH();
+        return GNMS_OK;
+    }
+    // every other mode: the layer's matrix gradient into the scratch matrix, then gnms_iou3d_backward (method 2) with the cuboids on both sides
+    const BoxesScratch s = cuboids_scratch(B, N, ld, overlap != nullptr);
+    GNMS_CHECK_ARG(scratch != nullptr && (uintptr_t)scratch % 256 == 0, "gnms_backward_cuboids: scratch is NULL or not 256-byte aligned");
+    if (scratch_bytes < s.total) {
+        gnms_set_error("gnms_backward_cuboids: scratch too small (%zu < %zu)", scratch_bytes, s.total);
+        return GNMS_ERR_WORKSPACE;
+    }
+    float* grad_iou = static_cast<float*>(scratch);
+    int rc;
+    if (!overlap) {                                                   // the forward's own writer, at the forward's threshold
+        float* m = reinterpret_cast<float*>(static_cast<char*>(scratch) + s.grad_iou);
+        if ((rc = gnms_nms_overlap3d_from_params(params3d, B, N, c.P.nms_threshold, m, ld, stream))) return rc;
+        overlap = m;
+    }
+    if ((rc = gnms_backward(grad_prob, scores, overlap, B, N, ld, counts, params, grad_scores, grad_iou, workspace, workspace_bytes, stream))) return rc;
+    return gnms_iou3d_backward(params3d, nullptr, grad_iou, B, N, N, ld, 2, grad_params3d, nullptr, static_cast<char*>(scratch) + s.grad_iou + s.iou,
+                               s.reduce, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
 // get_groups as a stand-alone entry (lib/groomed_nms.py:208-270)
 // ------------------------------------------------------------------------------------------------
 namespace {

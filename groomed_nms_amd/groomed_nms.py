@@ -140,8 +140,10 @@ class _LayerFunction(torch.autograd.Function):
     in one call (a seventh output, non-differentiable as the reference's loss feeds it, lib/loss/rpn_3d.py:791 `.clone().detach()`);
     _MODE_BOXES the layer from the boxes, no matrix at all.  box_grad: None, or the gnms_backward_boxes route (_BOX_ROUTES) when the 2D boxes
     require grad -- the backward then returns dL/dboxes too, what autograd gives the reference for
-    differentiable_nms(scores, iou(boxes, boxes)) when the caller does not detach the overlaps.
-    What is kept for the backward, and which backward entry runs, is the library's answer (gnms_backward_reads)."""
+    differentiable_nms(scores, iou(boxes, boxes)) when the caller does not detach the overlaps.  With _MODE_IOU3D the same switch asks for
+    dL/dparams3d [B,N,7] (gnms_backward_cuboids).
+    What is kept for the backward, and which backward entry runs, is the library's answer (gnms_backward_reads; for the cuboid gradient
+    its sibling gnms_backward_cuboids_reads)."""
 
     @staticmethod
     def forward(ctx, scores, src, counts, params, iou_out, mode, box_grad):
@@ -157,10 +159,13 @@ class _LayerFunction(torch.autograd.Function):
             matrix, ld = _matrix_layout(src)
         else:
             boxes = src.contiguous()
-        reads = lib.gnms_backward_reads(mode, p, ptr(boxes), route)
+        if mode == _MODE_IOU3D and route != _NO_BOX_GRAD:      # the cuboid gradient has its own table (gnms_backward_cuboids follows)
+            reads, asked = lib.gnms_backward_cuboids_reads(p, ptr(boxes), route), "gnms_backward_cuboids_reads"
+        else:
+            reads, asked = lib.gnms_backward_reads(mode, p, ptr(boxes), route), "gnms_backward_reads"
         if reads < 0:                         # (an empty call has no pointer to ask about, and its backward reads nothing)
             if scores_c.numel():
-                check(reads, "gnms_backward_reads")
+                check(reads, asked)
             reads = 0
         if reads & _COPY_BOXES:               # the box-gradient kernels load a box as one float4 (without a box gradient the forward
             boxes = boxes.clone()             # entries refuse an unaligned view themselves)
@@ -202,7 +207,14 @@ class _LayerFunction(torch.autograd.Function):
         grad_scores = torch.empty_like(scores_c)
         grad_src = None
         with on_device(dev):
-            if route != _NO_BOX_GRAD:
+            if route != _NO_BOX_GRAD and mode == _MODE_IOU3D:
+                grad_src = torch.empty((B, N, 7), dtype=torch.float32, device=dev)
+                nbytes = lib.gnms_backward_cuboids_scratch_bytes(B, N, ld, params, int(matrix is not None), route)
+                scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+                check(lib.gnms_backward_cuboids(ptr(grad_prob), ptr(boxes), ptr(scores_c), B, N, ptr(counts), params, ptr(grad_scores),
+                                                ptr(grad_src), ptr(matrix), ld, route, ptr(scratch), nbytes, ptr(ws), ws.numel(),
+                                                stream_ptr(dev)), "gnms_backward_cuboids")
+            elif route != _NO_BOX_GRAD:
                 grad_src = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
                 nbytes = lib.gnms_backward_boxes_scratch_bytes(B, N, ld, params, int(matrix is not None), route)
                 scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
@@ -373,13 +385,16 @@ def differentiable_nms_with_iou3d_batched(scores, params3d, counts=None, iou_out
                                           mask_group_boxes=True, group_size=100, index_lists=True):
     """scores [B,N], params3d [B,N,7] = (x3d, y3d, z3d, w3d, h3d, l3d, ry3d) -> (prob, order, valid, invalid, nvalid, ninvalid,
     overlap [B,N,N]): the 3D NMS overlap 0.5*(1+GIoU3D) of lib/loss/rpn_3d.py:778-784 AND the layer on it in one call; identical
-    to overlaps.iou3d_batched(from_params=True, nms_overlap=True) + differentiable_nms_batched."""
+    to overlaps.iou3d_batched(from_params=True, nms_overlap=True) + differentiable_nms_batched.  When params3d requires grad the backward
+    returns dL/dparams3d as well (BOX_GRAD_ROUTE picks the route, as for the 2D boxes); the returned overlap stays non-differentiable."""
     params = _params(nms_threshold, pruning_method, temperature, valid_box_prob_threshold, return_sorted_prob, group_boxes,
                      mask_group_boxes, group_size, False, bool(index_lists))
     if counts is not None:
         counts = counts.to(device=scores.device, dtype=torch.int32).contiguous()
     if params3d.shape[-1] != 7:
         raise ValueError("params3d must be [B, N, 7]")
+    if params3d.requires_grad and torch.is_grad_enabled():           # dL/dparams3d as well (DESIGN 3.24); without it the calls below, unchanged
+        return _LayerFunction.apply(scores.float(), params3d.float(), counts, params, iou_out, _MODE_IOU3D, _BOX_ROUTES[BOX_GRAD_ROUTE])
     ext = _binding()
     if ext and scores.is_cuda:
         return tuple(_layer(ext, scores.float(), params3d.float(), counts, iou_out, _MODE_IOU3D, params))

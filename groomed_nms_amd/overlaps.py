@@ -120,11 +120,59 @@ def iou_batched(boxes_a, boxes_b=None, out=None):
     return out
 
 
+class _Iou3dFunction(torch.autograd.Function):
+    """iou3d_batched(from_params=True) with the gradient w.r.t. the cuboids: the forward is the very call it makes without one, the
+    backward is gnms_iou3d_backward (csrc/iou3d_backward.hip) -- the reference's get_corners_of_cuboid + iou3d_approximate are torch
+    operations that autograd differentiates (lib/math_3d.py:364-435, lib/core.py:305-421); this is that derivative in closed form
+    (DESIGN 3.24).  params_b None: params_a on both sides.  The second (BEV) output of want_bev is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, params_a, params_b, method, want_bev, nms_overlap, nms_threshold):
+        a = params_a.contiguous()
+        b = None if params_b is None else params_b.contiguous()
+        ctx.save_for_backward(a, b)
+        ctx.method = 2 if nms_overlap else {"normal": 0, "generalized": 1}[method]
+        res = iou3d_batched(a.detach(), None if b is None else b.detach(), method=method, from_params=True, want_bev=want_bev,
+                            nms_overlap=nms_overlap, nms_threshold=nms_threshold)
+        if want_bev:
+            ctx.mark_non_differentiable(res[0])
+        ctx.want_bev = want_bev
+        return res
+
+    @staticmethod
+    def backward(ctx, *grads):
+        grad = grads[-1]                                              # (bev, iou_3d) with want_bev: the matrix is the last output
+        a, b = ctx.saved_tensors
+        if grad is None:
+            return (None,) * 6
+        lib = _lib.load()
+        B, M, _ = a.shape
+        N = M if b is None else b.shape[1]
+        grad, ld = _cotangent_layout(grad.float(), B, M, N)
+        d_a = torch.empty_like(a) if (b is None or ctx.needs_input_grad[0]) else None
+        d_b = torch.empty_like(b) if (b is not None and ctx.needs_input_grad[1]) else None
+        ws = torch.empty((max(lib.gnms_iou3d_backward_workspace_bytes(B, M, N), 256),), dtype=torch.uint8, device=a.device)
+        with on_device(a.device):
+            check(lib.gnms_iou3d_backward(ptr(a), ptr(b), ptr(grad), B, M, N, ld, ctx.method, ptr(d_a), ptr(d_b), ptr(ws), ws.numel(),
+                                          stream_ptr(a.device)), "gnms_iou3d_backward")
+        return d_a, d_b, None, None, None, None
+
+
 def iou3d_batched(a, b=None, method="generalized", from_params=False, want_bev=False, nms_overlap=False, out=None, nms_threshold=None):
     """a [B,M,3,8] corners (or [B,M,7] params when from_params) -> iou_3d [B,M,N] (and iou_bev).
     nms_overlap=True returns 0.5*(1+giou), the matrix both reference callers hand to the NMS.  With nms_threshold (the threshold
     the layer will apply; square from-params problems) the HBM-bound kernel of gnms_nms_overlap3d_from_params writes it: within
-    2e-6 of the exact operation order everywhere, and exactly that order wherever the threshold decision could depend on it."""
+    2e-6 of the exact operation order everywhere, and exactly that order wherever the threshold decision could depend on it.
+    from_params=True is differentiable w.r.t. the cuboids: when one of them requires grad the result carries a grad_fn
+    (gnms_iou3d_backward); otherwise it is a leaf, the same call as ever.  The corner form stays non-differentiable."""
+    if from_params and torch.is_grad_enabled() and (a.requires_grad or (b is not None and b.requires_grad)):
+        if out is not None:
+            raise ValueError("iou3d_batched: `out` cannot be given when the cuboids require grad")
+        if not a.is_cuda or a.dtype != torch.float32 or (b is not None and (b.dtype != torch.float32 or not b.is_cuda)):
+            raise TypeError("iou3d_batched: the gradient w.r.t. the cuboids needs CUDA float32 parameters")
+        if method not in ("normal", "generalized"):
+            raise ValueError("unknown method {}".format(method))
+        return _Iou3dFunction.apply(a, None if b is a else b, method, bool(want_bev), bool(nms_overlap), nms_threshold)
     lib = _lib.load()
     a = a.contiguous()
     if nms_overlap and from_params and b is None and nms_threshold is not None and not want_bev:

@@ -95,6 +95,25 @@ size_t gnms_iou2d_backward_workspace_bytes(int B, int M, int N);
 int gnms_iou2d_backward(const float* boxes_a, const float* boxes_b, const float* grad, int B, int M, int N, int64_t ld, float* d_boxes_a,
                         float* d_boxes_b, void* workspace, size_t workspace_bytes, void* stream);
 
+/* backward of gnms_iou3d_from_params (method 0, 1, 2) and of gnms_nms_overlap3d_from_params (method 2: its two expressions share one
+ * analytic derivative): the cotangent grad [B][M][ld] of the matrix contracted with d overlap / d cuboid, through the corner AABBs of
+ * get_corners_of_cuboid.
+ *   d_params_a [B][M][7] = sum_j grad[i][j] d f(a_i, b_j)/d a_i,  d_params_b [B][N][7] = sum_i grad[i][j] d f(a_i, b_j)/d b_j,
+ *   each row (x3d, y3d, z3d, w3d, h3d, l3d, ry3d).
+ * torch autograd's conventions for lib/core.py:305-421: a tied elementwise max / min of the two boxes' edges splits evenly; the x and z
+ * intersection extents pass the gradient at 0 (clamp), the y intersection extent and the three hull extents give 1/2 at exactly 0
+ * (torch.max(zeros, .)).  One deliberate difference: where a box's own corners tie (sin ry or cos ry exactly 0: ry = +-0 in float32)
+ * they share the gradient (sgn 0 = 0), so d ry is the symmetric value there; the reference sends it all to one unspecified corner.
+ * Ties and clamps are decided on the float32 extents the forward saw.  Either output may be NULL (not both).  params_b == NULL means
+ * params_a on both sides (M == N): both roles are summed into d_params_a, d_params_b must be NULL.  Every element of a given output is
+ * written.  A pair whose cotangent is exactly 0 contributes nothing; everything else is plain IEEE fp32.  grad is read once; the sums go
+ * through per-tile partial slabs in `workspace` (gnms_iou3d_backward_workspace_bytes(B, M, N) bytes, 256-byte aligned; it also holds
+ * the boxes' records) added in a fixed order: no float atomics, the same inputs give the same bits.  No alignment is asked of the
+ * parameters or the outputs (28-byte rows).  Stream-ordered, no allocation, graph-capturable. */
+size_t gnms_iou3d_backward_workspace_bytes(int B, int M, int N);
+int gnms_iou3d_backward(const float* params_a, const float* params_b, const float* grad, int B, int M, int N, int64_t ld, int method,
+                        float* d_params_a, float* d_params_b, void* workspace, size_t workspace_bytes, void* stream);
+
 /* get_corners_of_cuboid  lib/math_3d.py:364-435 (torch branch, iou_3d_convention=True).
  * params [count][7] = (x3d, y3d, z3d, w3d, h3d, l3d, ry3d) -> corners [count][3][8]. */
 int gnms_corners_of_cuboid(const float* params, int64_t count, float* corners, void* stream);
@@ -291,6 +310,9 @@ int gnms_backward_boxes(const float* grad_prob, const float* boxes, const float*
  *                        route DENSE, or any other mode                            READS_BOXES | READS_MATRIX  (pass the forward's matrix as `iou`
  *                                                                                                 where the entry wrote one, else NULL)
  *                        + boxes not 16-byte aligned                               | COPY_BOXES
+ *
+ * The cuboid gradient behind GNMS_ENTRY_WITH_IOU3D is not a row of this table (a box-gradient route with that entry stays an error
+ * here): ask its sibling, gnms_backward_cuboids_reads, below.
  */
 #define GNMS_ENTRY_MATRIX 0     /* gnms_forward */
 #define GNMS_ENTRY_WITH_IOU2D 1 /* gnms_forward_with_iou2d */
@@ -302,6 +324,29 @@ int gnms_backward_boxes(const float* grad_prob, const float* boxes, const float*
 #define GNMS_BWD_FROM_BOXES 4   /* the backward entry is gnms_backward_from_boxes */
 #define GNMS_BWD_COPY_BOXES 8   /* gnms_backward_boxes and the forward in front of it load a box as one float4: give BOTH a 16-byte aligned copy */
 int gnms_backward_reads(int entry, const gnms_params* params, const void* boxes, int box_grad_route);
+
+/* backward of L through prob WITH the gradient w.r.t. the cuboids params3d [B][N][7] the 3D NMS overlap was computed from: what autograd
+ * gives the reference for differentiable_nms(scores, 0.5 (1 + iou3d_approximate(corners(params), "generalized"))) when the caller does
+ * not detach.  Pairs with gnms_forward_with_iou3d (and with gnms_forward on gnms_nms_overlap3d_from_params' matrix at
+ * params->nms_threshold); scores / counts / params / workspace must be the ones the forward call saw.
+ *   grad_scores [B][N], grad_params3d [B][N][7] (input order), both fully overwritten; boxes behind counts[b] and boxes in no group get 0.
+ *   overlap     the forward's matrix [B][N][ld], or NULL: the dense route then rebuilds it in `scratch` with the forward's own writer
+ *               (gnms_nms_overlap3d_from_params at params->nms_threshold; that call allocates stream-ordered).
+ *   route       GNMS_BOXES_ROUTE_AUTO in the default mode: the SPARSE route -- gnms_backward, then one O(N) launch (a member's row is
+ *               one term, a head's row a sum over its run in member order), no N x N pass, no scratch, `overlap` not read; the
+ *               member's cotangent is (-(gx s_head)) f'(q) with q the matrix entry as the forward defines it (guard band included).
+ *               Every other mode, and GNMS_BOXES_ROUTE_DENSE for any mode: gnms_backward with grad_iou written into `scratch`, then
+ *               gnms_iou3d_backward (method 2) with the cuboids on both sides.
+ *   scratch     gnms_backward_cuboids_scratch_bytes(B, N, ld, params, overlap != NULL, route) bytes, 256-byte aligned (0 on the sparse route).
+ * A non-head member's gradient is the same bits on both routes (one term); a head's is a sum in member order on the sparse route.
+ * gnms_backward_cuboids_reads (host code only, the same gates): GNMS_BWD_READS_BOXES on the sparse route, GNMS_BWD_READS_BOXES |
+ * GNMS_BWD_READS_MATRIX otherwise; never COPY_BOXES (a 28-byte row is not loaded as a float4); negative with gnms_last_error set for
+ * NULL params / params3d or an unknown route. */
+size_t gnms_backward_cuboids_scratch_bytes(int B, int N, int64_t ld, const gnms_params* params, int have_overlap, int route);
+int gnms_backward_cuboids(const float* grad_prob, const float* params3d, const float* scores, int B, int N, const int32_t* counts,
+                          const gnms_params* params, float* grad_scores, float* grad_params3d, const float* overlap, int64_t ld, int route,
+                          void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int gnms_backward_cuboids_reads(const gnms_params* params, const void* params3d, int route);
 
 /* profiling hook: re-runs only the threshold bit-matrix kernel (the single full read of the overlap matrix, the
  * dominant kernel of gnms_forward) on a workspace a previous gnms_forward call filled. */
