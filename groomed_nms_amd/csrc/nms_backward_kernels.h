@@ -232,115 +232,97 @@ __global__ __launch_bounds__(256) void bwd_masked_iou_kernel(const float* __rest
     grad_iou[e] = (-(I.gx[q] * I.sscore[h])) * d;
 }
 
-// dL/dboxes of the masked-group layer (hard sort, unsorted output: bwd_masked_fused_kernel's / bwd_plan_kernel's modes) WITHOUT an N x N
-// pass: the layer's matrix gradient has one entry per non-head member k, at [member][head] (bwd_masked_iou_kernel), so
-//   member k : dL/dbox_k    = g_k * dIoU(box_k, box_head)/da          one term, a plain store
-//   head h   : dL/dbox_h    = sum_k g_k * dIoU(box_k, box_h)/db       sequentially in member order over the group's run
-//   g_k = (-(gx_k s_h)) f'(IoU(box_k, box_h)), the IoU recomputed from the boxes with the forward's operation order
+// dL/d(geometry) of the masked-group layer (hard sort, unsorted output: bwd_masked_fused_kernel's / bwd_plan_kernel's modes) WITHOUT an
+// N x N pass, for the 2D boxes behind gnms_forward_with_iou2d (MaskedBoxes) and the cuboids behind gnms_forward_with_iou3d
+// (MaskedCuboids).  The layer's matrix gradient has one entry per non-head member k, at [member][head]
+// (bwd_masked_iou_kernel), so
+//   member k : dL/dbox_k    = g_k * d f(box_k, box_head)/da          one term, a plain store
+//   head h   : dL/dbox_h    = sum_k g_k * d f(box_k, box_h)/db       sequentially in member order over the group's run
+//   g_k = (-(gx_k s_h)) f'(q), q the matrix entry of (member, head) recomputed from the boxes as the forward computed it
 // ONE launch with bwd_masked_fused_kernel's two kinds of workgroups: blockIdx.x < elem_blocks, one thread per rank (members; 0 for
 // boxes in no group, heads without members and boxes behind counts[b]); above, one WAVE per multi-member group (hlist): the lanes fetch
-// the members' terms in parallel, the four sums then run SEQUENTIALLY in member order (v_readlane + v_add), as dL/ds_head does.
-// The pair arithmetic is iou_grad.h's, with the member as the row box, exactly as gnms_iou2d_backward evaluates the same entry: a
-// member's gradient is the same bits on both routes.  Indices out of the workspace are clamped to the image.
-__device__ __forceinline__ float bwd_member_cotangent(const float* __restrict__ gp, const ImgPtrs& I, int k, int h, const gnms_iou_grad::Pair& p,
-                                                      const gnms_params& P) {
-    const float d = gnms_prune_grad(p.inter / p.uni, P.nms_threshold, P.temperature, P.pruning_method);
-    return (-(bwd_gx_of(gp, I, k) * I.sscore[h])) * d;
-}
-
-__global__ __launch_bounds__(256) void bwd_masked_boxes_kernel(const float* __restrict__ grad_prob, const float* __restrict__ boxes, int N,
-                                                               const int* __restrict__ counts, gnms_params P, char* ws, gnms_ws_layout L,
-                                                               float* __restrict__ grad_boxes, int elem_blocks) {
-    using namespace gnms_iou_grad;
-    const int b = blockIdx.y;
-    const int n = gnms_count(counts, b, N);
-    ImgPtrs I = img_ptrs(ws, L, b);
-    const float4* bx = reinterpret_cast<const float4*>(boxes) + (size_t)b * N;
-    float4* gb = reinterpret_cast<float4*>(grad_boxes) + (size_t)b * N;
-    const float* gp = grad_prob + (size_t)b * N;
-    const unsigned last = (unsigned)(n > 0 ? n - 1 : 0);
-    if ((int)blockIdx.x >= elem_blocks) {
-        if (n == 0) return;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const int nheads = min(I.misc[1], n);
-        const int nhb = (int)gridDim.x - elem_blocks;
-        for (int hi = ((int)blockIdx.x - elem_blocks) * 4 + wave; hi < nheads; hi += nhb * 4) {
-            const int k = (int)min((unsigned)I.hlist[hi], last);
-            const int hstart = I.gstart[k], hlen = I.glen[k];
-            if (hstart < 0 || hlen < 2 || hstart + hlen > n) continue;                    // (a workspace the forward never filled)
-            const int ck = (int)min((unsigned)I.order[k], last);
-            const float4 hb = bx[ck];
-            const float harea = box_area(hb);
-            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (int base = 1; base < hlen; base += 64) {
-                const int t = base + lane;
-                float term[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (t < hlen) {
-                    const int mk = (int)min((unsigned)I.gsorted[hstart + t], last);
-                    const float4 a = bx[min((unsigned)I.order[mk], last)];
-                    const Pair p = pair_of(a, box_area(a), hb, harea);
-                    add_box_grad(hb, a, p, bwd_member_cotangent(gp, I, mk, k, p, P), term);
-                }
-                const int cnt = min(64, hlen - base);
-                for (int u = 0; u < cnt; ++u) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) acc[c] += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(term[c]), u));
-                }
-            }
-            if (lane == 0) gb[ck] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        }
-        return;
-    }
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= N) return;
-    if (k >= n) { gb[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); return; }
-    const int ck = (int)min((unsigned)I.order[k], last);
-    const int h = I.head[k];
-    if (h == k && I.glen[k] > 1 && I.misc[1] > 0) return;            // written by the head waves (hlist holds exactly these)
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (h >= 0 && h != k && h < n) {
-        const float4 a = bx[ck], hb = bx[min((unsigned)I.order[h], last)];
-        const Pair p = pair_of(a, box_area(a), hb, box_area(hb));
-        add_box_grad(a, hb, p, bwd_member_cotangent(gp, I, k, h, p, P), acc);
-    }
-    gb[ck] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-}
-
-// dL/dparams3d of the masked-group layer behind gnms_forward_with_iou3d: bwd_masked_boxes_kernel for cuboids.  The same two
-// kinds of workgroups and the same order of the sums; a box's record is rebuilt from its seven parameters (the forward's floats:
-// corners_of + aabb_record), the matrix entry q of (member, head) is the forward's own definition (nms_overlap3d_pair, guard band
-// included), the pair arithmetic is iou3d_grad.h's with the member as the row box, exactly as gnms_iou3d_backward<method 2> evaluates
-// the same entry.  Six extent sums per box, carried to the seven parameters ONCE per box (params_grad).
-struct CuboidRec {
-    float4 u, v, e;
-};
-__device__ __forceinline__ CuboidRec cuboid_rec(const float* __restrict__ p) {
-    CuboidRec r;
-    gnms_iou3d_grad::record_of_params(p, r.u, r.v, r.e);
-    return r;
-}
-__device__ __forceinline__ float bwd_member_cotangent3d(const float* __restrict__ gp, const ImgPtrs& I, int k, int h, const CuboidRec& member,
-                                                        const CuboidRec& head, const gnms_params& P) {
-    const float q = gnms_iou3d::nms_overlap3d_pair(member.u, member.v, member.e, head.u, head.v, head.e, P.nms_threshold);
+// the members' terms in parallel, the G::kAcc sums then run SEQUENTIALLY in member order (v_readlane + v_add), as dL/ds_head does.
+// The pair arithmetic is iou_grad.h's / iou3d_grad.h's, with the member as the row box, exactly as gnms_iou2d_backward /
+// gnms_iou3d_backward<method 2> evaluates the same entry: a member's gradient is the same bits on both routes.  Indices out of the
+// workspace are clamped to the image.
+//
+// A geometry G: kAcc sums and kFloats floats per box; Box, what a thread holds of an input row, and load(rows, index); Pair, pair(a, b)
+// and add_grad(s, o, pair, g, acc) as the walker's (pair_grad_walker.h); entry(member, head, pair, P), the recomputed matrix entry;
+// store(rows, out, index, acc), a finished sum to the output row, and store_zero(out, index) behind counts[b].
+__device__ __forceinline__ float bwd_member_cotangent(const float* __restrict__ gp, const ImgPtrs& I, int k, int h, float q, const gnms_params& P) {
     const float d = gnms_prune_grad(q, P.nms_threshold, P.temperature, P.pruning_method);
     return (-(bwd_gx_of(gp, I, k) * I.sscore[h])) * d;
 }
-__device__ __forceinline__ void store_params_grad(const float* __restrict__ p, const float (&G)[6], float* __restrict__ out) {
-    float d[7];
-    gnms_iou3d_grad::params_grad(p, G, d);
-#pragma unroll
-    for (int c = 0; c < 7; ++c) out[c] = d[c];
-}
 
-__global__ __launch_bounds__(256) void bwd_masked_cuboids_kernel(const float* __restrict__ grad_prob, const float* __restrict__ params3d, int N,
-                                                                 const int* __restrict__ counts, gnms_params P, char* ws, gnms_ws_layout L,
-                                                                 float* __restrict__ grad_params, int elem_blocks) {
-    using namespace gnms_iou3d_grad;
+struct MaskedBoxes {
+    static constexpr int kAcc = 4, kFloats = 4;
+    struct Box {
+        float4 b;
+        float area;
+    };
+    using Pair = gnms_iou_grad::Pair;
+    static __device__ __forceinline__ Box load(const float* __restrict__ rows, size_t i) {
+        const float4 b = reinterpret_cast<const float4*>(rows)[i];
+        return Box{b, gnms_iou_grad::box_area(b)};
+    }
+    static __device__ __forceinline__ Pair pair(const Box& a, const Box& b) { return gnms_iou_grad::pair_of(a.b, a.area, b.b, b.area); }
+    static __device__ __forceinline__ float entry(const Box&, const Box&, const Pair& p, const gnms_params&) { return p.inter / p.uni; }
+    static __device__ __forceinline__ void add_grad(const Box& s, const Box& o, const Pair& p, float g, float (&acc)[4]) {
+        gnms_iou_grad::add_box_grad(s.b, o.b, p, g, acc);
+    }
+    static __device__ __forceinline__ void store(const float* __restrict__, float* __restrict__ out, size_t i, const float (&acc)[4]) {
+        reinterpret_cast<float4*>(out)[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    }
+    static __device__ __forceinline__ void store_zero(float* __restrict__ out, size_t i) {
+        reinterpret_cast<float4*>(out)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+};
+
+// A cuboid's record is rebuilt from its seven parameters (the forward's floats: corners_of + aabb_record), the matrix entry is the
+// forward's own definition (nms_overlap3d_pair, guard band included).  Six extent sums per box, carried to the seven parameters ONCE
+// per box (params_grad).
+struct MaskedCuboids {
+    static constexpr int kAcc = 6, kFloats = 7;
+    struct Box {
+        float4 u, v, e;                                               // the record, for the matrix entry
+        gnms_iou3d_grad::Rec r;                                       // rec_of(u, v), for the gradient
+    };
+    using Pair = gnms_iou3d_grad::Pair;
+    static __device__ __forceinline__ Box load(const float* __restrict__ rows, size_t i) {
+        Box c;
+        gnms_iou3d_grad::record_of_params(rows + i * 7, c.u, c.v, c.e);
+        c.r = gnms_iou3d_grad::rec_of(c.u, c.v);
+        return c;
+    }
+    static __device__ __forceinline__ Pair pair(const Box& a, const Box& b) { return gnms_iou3d_grad::pair_of(a.r, b.r); }
+    static __device__ __forceinline__ float entry(const Box& member, const Box& head, const Pair&, const gnms_params& P) {
+        return gnms_iou3d::nms_overlap3d_pair(member.u, member.v, member.e, head.u, head.v, head.e, P.nms_threshold);
+    }
+    static __device__ __forceinline__ void add_grad(const Box& s, const Box& o, const Pair& p, float g, float (&acc)[6]) {
+        gnms_iou3d_grad::add_extent_grad<2>(s.r, o.r, p, g, acc);
+    }
+    static __device__ __forceinline__ void store(const float* __restrict__ rows, float* __restrict__ out, size_t i, const float (&acc)[6]) {
+        float d[7];
+        gnms_iou3d_grad::params_grad(rows + i * 7, acc, d);
+#pragma unroll
+        for (int c = 0; c < 7; ++c) out[i * 7 + c] = d[c];
+    }
+    static __device__ __forceinline__ void store_zero(float* __restrict__ out, size_t i) {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) out[i * 7 + c] = 0.0f;
+    }
+};
+
+template <class G>
+__global__ __launch_bounds__(256) void bwd_masked_geometry_kernel(const float* __restrict__ grad_prob, const float* __restrict__ rows, int N,
+                                                                  const int* __restrict__ counts, gnms_params P, char* ws, gnms_ws_layout L,
+                                                                  float* __restrict__ grad_rows, int elem_blocks) {
+    using Box = typename G::Box;
     const int b = blockIdx.y;
     const int n = gnms_count(counts, b, N);
     ImgPtrs I = img_ptrs(ws, L, b);
-    const float* px = params3d + (size_t)b * N * 7;
-    float* gb = grad_params + (size_t)b * N * 7;
+    const float* px = rows + (size_t)b * N * G::kFloats;
+    float* gb = grad_rows + (size_t)b * N * G::kFloats;
     const float* gp = grad_prob + (size_t)b * N;
     const unsigned last = (unsigned)(n > 0 ? n - 1 : 0);
     if ((int)blockIdx.x >= elem_blocks) {
@@ -353,47 +335,46 @@ __global__ __launch_bounds__(256) void bwd_masked_cuboids_kernel(const float* __
             const int hstart = I.gstart[k], hlen = I.glen[k];
             if (hstart < 0 || hlen < 2 || hstart + hlen > n) continue;                    // (a workspace the forward never filled)
             const int ck = (int)min((unsigned)I.order[k], last);
-            const CuboidRec hr = cuboid_rec(px + (size_t)ck * 7);
-            const Rec hb = rec_of(hr.u, hr.v);
-            float acc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            const Box hb = G::load(px, ck);
+            float acc[G::kAcc];
+#pragma unroll
+            for (int c = 0; c < G::kAcc; ++c) acc[c] = 0.0f;
             for (int base = 1; base < hlen; base += 64) {
                 const int t = base + lane;
-                float term[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                float term[G::kAcc];
+#pragma unroll
+                for (int c = 0; c < G::kAcc; ++c) term[c] = 0.0f;
                 if (t < hlen) {
                     const int mk = (int)min((unsigned)I.gsorted[hstart + t], last);
-                    const CuboidRec mr = cuboid_rec(px + (size_t)min((unsigned)I.order[mk], last) * 7);
-                    const Rec a = rec_of(mr.u, mr.v);
-                    const Pair p = pair_of(a, hb);
-                    add_extent_grad<2>(hb, a, p, bwd_member_cotangent3d(gp, I, mk, k, mr, hr, P), term);
+                    const Box a = G::load(px, min((unsigned)I.order[mk], last));
+                    const typename G::Pair p = G::pair(a, hb);
+                    G::add_grad(hb, a, p, bwd_member_cotangent(gp, I, mk, k, G::entry(a, hb, p, P), P), term);
                 }
                 const int cnt = min(64, hlen - base);
                 for (int u = 0; u < cnt; ++u) {
 #pragma unroll
-                    for (int c = 0; c < 6; ++c) acc[c] += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(term[c]), u));
+                    for (int c = 0; c < G::kAcc; ++c) acc[c] += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(term[c]), u));
                 }
             }
-            if (lane == 0) store_params_grad(px + (size_t)ck * 7, acc, gb + (size_t)ck * 7);
+            if (lane == 0) G::store(px, gb, ck, acc);
         }
         return;
     }
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= N) return;
-    if (k >= n) {
-#pragma unroll
-        for (int c = 0; c < 7; ++c) gb[(size_t)k * 7 + c] = 0.0f;
-        return;
-    }
+    if (k >= n) { G::store_zero(gb, k); return; }
     const int ck = (int)min((unsigned)I.order[k], last);
     const int h = I.head[k];
     if (h == k && I.glen[k] > 1 && I.misc[1] > 0) return;            // written by the head waves (hlist holds exactly these)
-    float acc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    float acc[G::kAcc];
+#pragma unroll
+    for (int c = 0; c < G::kAcc; ++c) acc[c] = 0.0f;
     if (h >= 0 && h != k && h < n) {
-        const CuboidRec mr = cuboid_rec(px + (size_t)ck * 7), hr = cuboid_rec(px + (size_t)min((unsigned)I.order[h], last) * 7);
-        const Rec a = rec_of(mr.u, mr.v), hb = rec_of(hr.u, hr.v);
-        const Pair p = pair_of(a, hb);
-        add_extent_grad<2>(a, hb, p, bwd_member_cotangent3d(gp, I, k, h, mr, hr, P), acc);
+        const Box a = G::load(px, ck), hb = G::load(px, min((unsigned)I.order[h], last));
+        const typename G::Pair p = G::pair(a, hb);
+        G::add_grad(a, hb, p, bwd_member_cotangent(gp, I, k, h, G::entry(a, hb, p, P), P), acc);
     }
-    store_params_grad(px + (size_t)ck * 7, acc, gb + (size_t)ck * 7);
+    G::store(px, gb, ck, acc);
 }
 
 }  // namespace gnms

@@ -1290,75 +1290,98 @@ extern "C" int gnms_backward_from_boxes(const float* grad_prob, const float* box
 }
 
 // ------------------------------------------------------------------------------------------------
-// backward with the gradient w.r.t. the boxes
+// backward with the gradient w.r.t. the geometry: the 2D boxes of gnms_forward_with_iou2d, the cuboids of
+// gnms_forward_with_iou3d.  One body, backward_geometry<G>; G adds to the masked kernel's geometry what the dense route calls.
 // ------------------------------------------------------------------------------------------------
 namespace {
-struct BoxesScratch { size_t grad_iou, iou, reduce, total; };
-BoxesScratch boxes_scratch(int B, int N, int64_t ld, bool have_iou) {
-    BoxesScratch s;
+struct BoxesBackward : MaskedBoxes {
+    static constexpr bool kAlign16 = true;                           // the kernels load a box, and store its gradient, as one float4
+    static int write_matrix(const float* boxes, int B, int N, const gnms_params&, float* m, int64_t ld, void* stream) {
+        return gnms_iou2d(boxes, boxes, B, N, N, m, ld, stream);
+    }
+    static size_t pair_workspace_bytes(int B, int N) { return gnms_iou2d_backward_workspace_bytes(B, N, N); }
+    static int pair_backward(const float* boxes, const float* grad_iou, int B, int N, int64_t ld, float* grad_boxes, void* ws, size_t bytes, void* stream) {
+        return gnms_iou2d_backward(boxes, nullptr, grad_iou, B, N, N, ld, grad_boxes, nullptr, ws, bytes, stream);
+    }
+};
+struct CuboidsBackward : MaskedCuboids {
+    static constexpr bool kAlign16 = false;
+    static int write_matrix(const float* params3d, int B, int N, const gnms_params& P, float* m, int64_t ld, void* stream) {
+        return gnms_nms_overlap3d_from_params(params3d, B, N, P.nms_threshold, m, ld, stream);    // the forward's own writer, at its threshold
+    }
+    static size_t pair_workspace_bytes(int B, int N) { return gnms_iou3d_backward_workspace_bytes(B, N, N); }
+    static int pair_backward(const float* params3d, const float* grad_iou, int B, int N, int64_t ld, float* grad_params3d, void* ws, size_t bytes,
+                             void* stream) {
+        return gnms_iou3d_backward(params3d, nullptr, grad_iou, B, N, N, ld, 2, grad_params3d, nullptr, ws, bytes, stream);
+    }
+};
+
+// the dense route's scratch: the matrix gradient | the matrix, where the caller kept none | the pair backward's workspace
+struct GeometryScratch { size_t grad_iou, iou, reduce, total; };
+template <class G>
+GeometryScratch geometry_scratch(int B, int N, int64_t ld, bool have_matrix) {
+    GeometryScratch s;
     s.grad_iou = gnms_align_up(sizeof(float) * (size_t)B * N * ld, 256);
-    s.iou = have_iou ? 0 : s.grad_iou;
-    s.reduce = gnms_iou2d_backward_workspace_bytes(B, N, N);
+    s.iou = have_matrix ? 0 : s.grad_iou;
+    s.reduce = G::pair_workspace_bytes(B, N);
     s.total = s.grad_iou + s.iou + s.reduce;
     return s;
+}
+template <class G>
+size_t geometry_scratch_bytes(int B, int N, int64_t ld, const gnms_params* params, int have_matrix, int route) {
+    if (!params || B <= 0 || N <= 0 || ld < N || boxes_sparse_route(*params, route)) return 0;
+    return geometry_scratch<G>(B, N, ld, have_matrix != 0).total;
+}
+
+template <class G>
+int backward_geometry(const char* name, const float* grad_prob, const float* rows, const float* scores, int B, int N, const int32_t* counts,
+                      const gnms_params* params, float* grad_scores, float* grad_rows, const float* matrix, int64_t ld, int route, void* scratch,
+                      size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    LayerCall c;
+    char null_msg[64];
+    snprintf(null_msg, sizeof(null_msg), "%s: null pointer", name);
+    GNMS_CHECK_ARG(route == GNMS_BOXES_ROUTE_AUTO || route == GNMS_BOXES_ROUTE_DENSE, "%s: unknown route %d", name, route);
+    GNMS_BEGIN_CALL(name, &c, B, N, ld, counts, params, workspace, workspace_bytes, stream, false,
+                    grad_prob && rows && scores && grad_scores && grad_rows, null_msg);
+    if (G::kAlign16) GNMS_CHECK_ARG(aligned16(rows) && aligned16(grad_rows), "%s: boxes and grad_boxes must be 16-byte aligned", name);
+    int rc;
+    if (boxes_sparse_route(c.P, route)) {
+        // (the masked backward never dereferences the matrix pointer when no matrix gradient is asked for)
+        if ((rc = gnms_backward(grad_prob, scores, rows, B, N, N, counts, params, grad_scores, nullptr, workspace, workspace_bytes, stream))) return rc;
+        const int elem_blocks = gnms_div_up(N, 256), head_blocks = N >= 2048 ? 128 : gnms_div_up(N, 16);
+        bwd_masked_geometry_kernel<G><<<dim3(elem_blocks + head_blocks, B), 256, 0, c.st>>>(grad_prob, rows, N, counts, c.P, c.ws, c.L, grad_rows,
+                                                                                            elem_blocks);
+        GNMS_CHECK_LAUNCH();
+        return GNMS_OK;
+    }
+    // every other mode: the layer's matrix gradient into the scratch matrix, then the pair backward with the geometry on both sides
+    const GeometryScratch s = geometry_scratch<G>(B, N, ld, matrix != nullptr);
+    GNMS_CHECK_ARG(scratch != nullptr && (uintptr_t)scratch % 256 == 0, "%s: scratch is NULL or not 256-byte aligned", name);
+    if (scratch_bytes < s.total) {
+        gnms_set_error("%s: scratch too small (%zu < %zu)", name, scratch_bytes, s.total);
+        return GNMS_ERR_WORKSPACE;
+    }
+    float* grad_iou = static_cast<float*>(scratch);
+    if (!matrix) {
+        float* m = reinterpret_cast<float*>(static_cast<char*>(scratch) + s.grad_iou);
+        if ((rc = G::write_matrix(rows, B, N, c.P, m, ld, stream))) return rc;
+        matrix = m;
+    }
+    if ((rc = gnms_backward(grad_prob, scores, matrix, B, N, ld, counts, params, grad_scores, grad_iou, workspace, workspace_bytes, stream))) return rc;
+    return G::pair_backward(rows, grad_iou, B, N, ld, grad_rows, static_cast<char*>(scratch) + s.grad_iou + s.iou, s.reduce, stream);
 }
 }  // namespace
 
 extern "C" size_t gnms_backward_boxes_scratch_bytes(int B, int N, int64_t ld, const gnms_params* params, int have_iou, int route) {
-    if (!params || B <= 0 || N <= 0 || ld < N || boxes_sparse_route(*params, route)) return 0;
-    return boxes_scratch(B, N, ld, have_iou != 0).total;
+    return geometry_scratch_bytes<BoxesBackward>(B, N, ld, params, have_iou, route);
 }
 
 extern "C" int gnms_backward_boxes(const float* grad_prob, const float* boxes, const float* scores, int B, int N, const int32_t* counts,
                                    const gnms_params* params, float* grad_scores, float* grad_boxes, const float* iou, int64_t ld, int route,
                                    void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream) {
-    LayerCall c;
-    GNMS_CHECK_ARG(route == GNMS_BOXES_ROUTE_AUTO || route == GNMS_BOXES_ROUTE_DENSE, "gnms_backward_boxes: unknown route %d", route);
-    GNMS_BEGIN_CALL("gnms_backward_boxes", &c, B, N, ld, counts, params, workspace, workspace_bytes, stream, false,
-                    grad_prob && boxes && scores && grad_scores && grad_boxes, "gnms_backward_boxes: null pointer");
-    GNMS_CHECK_ARG(aligned16(boxes) && aligned16(grad_boxes), "gnms_backward_boxes: boxes and grad_boxes must be 16-byte aligned");
-    if (boxes_sparse_route(c.P, route)) {
-        // (the masked backward never dereferences the matrix pointer when no matrix gradient is asked for)
-        const int rc = gnms_backward(grad_prob, scores, boxes, B, N, N, counts, params, grad_scores, nullptr, workspace, workspace_bytes, stream);
-        if (rc) return rc;
-        const int elem_blocks = gnms_div_up(N, 256), head_blocks = N >= 2048 ? 128 : gnms_div_up(N, 16);
-        bwd_masked_boxes_kernel<<<dim3(elem_blocks + head_blocks, B), 256, 0, c.st>>>(grad_prob, boxes, N, counts, c.P, c.ws, c.L, grad_boxes,
-                                                                                      elem_blocks);
-        GNMS_CHECK_LAUNCH();
-        return GNMS_OK;
-    }
-    // every other mode: the layer's matrix gradient into the scratch matrix, then gnms_iou2d_backward with the boxes on both sides
-    const BoxesScratch s = boxes_scratch(B, N, ld, iou != nullptr);
-    GNMS_CHECK_ARG(scratch != nullptr && (uintptr_t)scratch % 256 == 0, "gnms_backward_boxes: scratch is NULL or not 256-byte aligned");
-    if (scratch_bytes < s.total) {
-        gnms_set_error("gnms_backward_boxes: scratch too small (%zu < %zu)", scratch_bytes, s.total);
-        return GNMS_ERR_WORKSPACE;
-    }
-    float* grad_iou = static_cast<float*>(scratch);
-    int rc;
-    if (!iou) {
-        float* m = reinterpret_cast<float*>(static_cast<char*>(scratch) + s.grad_iou);
-        if ((rc = gnms_iou2d(boxes, boxes, B, N, N, m, ld, stream))) return rc;
-        iou = m;
-    }
-    if ((rc = gnms_backward(grad_prob, scores, iou, B, N, ld, counts, params, grad_scores, grad_iou, workspace, workspace_bytes, stream))) return rc;
-    return gnms_iou2d_backward(boxes, nullptr, grad_iou, B, N, N, ld, grad_boxes, nullptr, static_cast<char*>(scratch) + s.grad_iou + s.iou, s.reduce,
-                               stream);
+    return backward_geometry<BoxesBackward>("gnms_backward_boxes", grad_prob, boxes, scores, B, N, counts, params, grad_scores, grad_boxes, iou, ld, route,
+                                            scratch, scratch_bytes, workspace, workspace_bytes, stream);
 }
-
-// ------------------------------------------------------------------------------------------------
-// backward with the gradient w.r.t. the cuboids: gnms_backward_boxes for gnms_forward_with_iou3d
-// ------------------------------------------------------------------------------------------------
-namespace {
-BoxesScratch cuboids_scratch(int B, int N, int64_t ld, bool have_overlap) {
-    BoxesScratch s;
-    s.grad_iou = gnms_align_up(sizeof(float) * (size_t)B * N * ld, 256);
-    s.iou = have_overlap ? 0 : s.grad_iou;
-    s.reduce = gnms_iou3d_backward_workspace_bytes(B, N, N);
-    s.total = s.grad_iou + s.iou + s.reduce;
-    return s;
-}
-}  // namespace
 
 // host code only (the table stands in include/groomed_nms_hip.h); the same gate as gnms_backward_cuboids branches on
 extern "C" int gnms_backward_cuboids_reads(const gnms_params* params, const void* params3d, int route) {
@@ -1369,44 +1392,14 @@ extern "C" int gnms_backward_cuboids_reads(const gnms_params* params, const void
 }
 
 extern "C" size_t gnms_backward_cuboids_scratch_bytes(int B, int N, int64_t ld, const gnms_params* params, int have_overlap, int route) {
-    if (!params || B <= 0 || N <= 0 || ld < N || boxes_sparse_route(*params, route)) return 0;
-    return cuboids_scratch(B, N, ld, have_overlap != 0).total;
+    return geometry_scratch_bytes<CuboidsBackward>(B, N, ld, params, have_overlap, route);
 }
 
 extern "C" int gnms_backward_cuboids(const float* grad_prob, const float* params3d, const float* scores, int B, int N, const int32_t* counts,
                                      const gnms_params* params, float* grad_scores, float* grad_params3d, const float* overlap, int64_t ld,
                                      int route, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream) {
-    LayerCall c;
-    GNMS_CHECK_ARG(route == GNMS_BOXES_ROUTE_AUTO || route == GNMS_BOXES_ROUTE_DENSE, "gnms_backward_cuboids: unknown route %d", route);
-    GNMS_BEGIN_CALL("gnms_backward_cuboids", &c, B, N, ld, counts, params, workspace, workspace_bytes, stream, false,
-                    grad_prob && params3d && scores && grad_scores && grad_params3d, "gnms_backward_cuboids: null pointer");
-    if (boxes_sparse_route(c.P, route)) {
-        // (the masked backward never dereferences the matrix pointer when no matrix gradient is asked for)
-        const int rc = gnms_backward(grad_prob, scores, params3d, B, N, N, counts, params, grad_scores, nullptr, workspace, workspace_bytes, stream);
-        if (rc) return rc;
-        const int elem_blocks = gnms_div_up(N, 256), head_blocks = N >= 2048 ? 128 : gnms_div_up(N, 16);
-        bwd_masked_cuboids_kernel<<<dim3(elem_blocks + head_blocks, B), 256, 0, c.st>>>(grad_prob, params3d, N, counts, c.P, c.ws, c.L, grad_params3d,
-                                                                                        elem_blocks);
-        GNMS_CHECK_LAUNCH();
-        return GNMS_OK;
-    }
-    // every other mode: the layer's matrix gradient into the scratch matrix, then gnms_iou3d_backward (method 2) with the cuboids on both sides
-    const BoxesScratch s = cuboids_scratch(B, N, ld, overlap != nullptr);
-    GNMS_CHECK_ARG(scratch != nullptr && (uintptr_t)scratch % 256 == 0, "gnms_backward_cuboids: scratch is NULL or not 256-byte aligned");
-    if (scratch_bytes < s.total) {
-        gnms_set_error("gnms_backward_cuboids: scratch too small (%zu < %zu)", scratch_bytes, s.total);
-        return GNMS_ERR_WORKSPACE;
-    }
-    float* grad_iou = static_cast<float*>(scratch);
-    int rc;
-    if (!overlap) {                                                   // the forward's own writer, at the forward's threshold
-        float* m = reinterpret_cast<float*>(static_cast<char*>(scratch) + s.grad_iou);
-        if ((rc = gnms_nms_overlap3d_from_params(params3d, B, N, c.P.nms_threshold, m, ld, stream))) return rc;
-        overlap = m;
-    }
-    if ((rc = gnms_backward(grad_prob, scores, overlap, B, N, ld, counts, params, grad_scores, grad_iou, workspace, workspace_bytes, stream))) return rc;
-    return gnms_iou3d_backward(params3d, nullptr, grad_iou, B, N, N, ld, 2, grad_params3d, nullptr, static_cast<char*>(scratch) + s.grad_iou + s.iou,
-                               s.reduce, stream);
+    return backward_geometry<CuboidsBackward>("gnms_backward_cuboids", grad_prob, params3d, scores, B, N, counts, params, grad_scores, grad_params3d,
+                                              overlap, ld, route, scratch, scratch_bytes, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

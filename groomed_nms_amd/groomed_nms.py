@@ -207,20 +207,13 @@ class _LayerFunction(torch.autograd.Function):
         grad_scores = torch.empty_like(scores_c)
         grad_src = None
         with on_device(dev):
-            if route != _NO_BOX_GRAD and mode == _MODE_IOU3D:
-                grad_src = torch.empty((B, N, 7), dtype=torch.float32, device=dev)
-                nbytes = lib.gnms_backward_cuboids_scratch_bytes(B, N, ld, params, int(matrix is not None), route)
+            if route != _NO_BOX_GRAD:
+                what, floats = ("gnms_backward_cuboids", 7) if mode == _MODE_IOU3D else ("gnms_backward_boxes", 4)
+                grad_src = torch.empty((B, N, floats), dtype=torch.float32, device=dev)
+                nbytes = getattr(lib, what + "_scratch_bytes")(B, N, ld, params, int(matrix is not None), route)
                 scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
-                check(lib.gnms_backward_cuboids(ptr(grad_prob), ptr(boxes), ptr(scores_c), B, N, ptr(counts), params, ptr(grad_scores),
-                                                ptr(grad_src), ptr(matrix), ld, route, ptr(scratch), nbytes, ptr(ws), ws.numel(),
-                                                stream_ptr(dev)), "gnms_backward_cuboids")
-            elif route != _NO_BOX_GRAD:
-                grad_src = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
-                nbytes = lib.gnms_backward_boxes_scratch_bytes(B, N, ld, params, int(matrix is not None), route)
-                scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
-                check(lib.gnms_backward_boxes(ptr(grad_prob), ptr(boxes), ptr(scores_c), B, N, ptr(counts), params, ptr(grad_scores),
-                                              ptr(grad_src), ptr(matrix), ld, route, ptr(scratch), nbytes, ptr(ws), ws.numel(),
-                                              stream_ptr(dev)), "gnms_backward_boxes")
+                check(getattr(lib, what)(ptr(grad_prob), ptr(boxes), ptr(scores_c), B, N, ptr(counts), params, ptr(grad_scores), ptr(grad_src),
+                                         ptr(matrix), ld, route, ptr(scratch), nbytes, ptr(ws), ws.numel(), stream_ptr(dev)), what)
             elif from_boxes:
                 check(lib.gnms_backward_from_boxes(ptr(grad_prob), ptr(boxes), ptr(scores_c), B, N, ptr(counts), params, ptr(grad_scores),
                                                    ptr(ws), ws.numel(), stream_ptr(dev)), "gnms_backward_from_boxes")

@@ -62,6 +62,24 @@ def _cotangent_layout(grad, B, M, N):
     return grad.contiguous(), N          # (also where a size-1 dimension carries an arbitrary stride: the copy is then free)
 
 
+def _pair_backward(ctx, grad, entry, *method):
+    """(d_a, d_b) of an overlap matrix's cotangent `grad` [B, M, N]: the body of _Iou2dFunction.backward and _Iou3dFunction.backward.
+    ctx saved (a, b), b None for a on both sides; `entry` names the library's backward (its workspace query is entry + "_workspace_bytes");
+    `method` is gnms_iou3d_backward's extra argument."""
+    a, b = ctx.saved_tensors
+    lib = _lib.load()
+    B, M, _ = a.shape
+    N = M if b is None else b.shape[1]
+    grad, ld = _cotangent_layout(grad.float(), B, M, N)
+    d_a = torch.empty_like(a) if (b is None or ctx.needs_input_grad[0]) else None
+    d_b = torch.empty_like(b) if (b is not None and ctx.needs_input_grad[1]) else None
+    ws = torch.empty((max(getattr(lib, entry + "_workspace_bytes")(B, M, N), 256),), dtype=torch.uint8, device=a.device)
+    with on_device(a.device):
+        check(getattr(lib, entry)(ptr(a), ptr(b), ptr(grad), B, M, N, ld, *method, ptr(d_a), ptr(d_b), ptr(ws), ws.numel(),
+                                  stream_ptr(a.device)), entry)
+    return d_a, d_b
+
+
 class _Iou2dFunction(torch.autograd.Function):
     """iou_batched with the gradient w.r.t. the boxes: the forward is the same gnms_iou2d launch, the backward is
     gnms_iou2d_backward (csrc/iou_backward.hip) -- the reference's iou() is a few torch operations that autograd differentiates
@@ -76,18 +94,7 @@ class _Iou2dFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
-        a, b = ctx.saved_tensors
-        lib = _lib.load()
-        B, M, _ = a.shape
-        N = M if b is None else b.shape[1]
-        grad, ld = _cotangent_layout(grad.float(), B, M, N)
-        d_a = torch.empty_like(a) if (b is None or ctx.needs_input_grad[0]) else None
-        d_b = torch.empty_like(b) if (b is not None and ctx.needs_input_grad[1]) else None
-        ws = torch.empty((max(lib.gnms_iou2d_backward_workspace_bytes(B, M, N), 256),), dtype=torch.uint8, device=a.device)
-        with on_device(a.device):
-            check(lib.gnms_iou2d_backward(ptr(a), ptr(b), ptr(grad), B, M, N, ld, ptr(d_a), ptr(d_b), ptr(ws), ws.numel(),
-                                          stream_ptr(a.device)), "gnms_iou2d_backward")
-        return d_a, d_b
+        return _pair_backward(ctx, grad, "gnms_iou2d_backward")
 
 
 def iou_batched(boxes_a, boxes_b=None, out=None):
@@ -142,20 +149,9 @@ class _Iou3dFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         grad = grads[-1]                                              # (bev, iou_3d) with want_bev: the matrix is the last output
-        a, b = ctx.saved_tensors
         if grad is None:
             return (None,) * 6
-        lib = _lib.load()
-        B, M, _ = a.shape
-        N = M if b is None else b.shape[1]
-        grad, ld = _cotangent_layout(grad.float(), B, M, N)
-        d_a = torch.empty_like(a) if (b is None or ctx.needs_input_grad[0]) else None
-        d_b = torch.empty_like(b) if (b is not None and ctx.needs_input_grad[1]) else None
-        ws = torch.empty((max(lib.gnms_iou3d_backward_workspace_bytes(B, M, N), 256),), dtype=torch.uint8, device=a.device)
-        with on_device(a.device):
-            check(lib.gnms_iou3d_backward(ptr(a), ptr(b), ptr(grad), B, M, N, ld, ctx.method, ptr(d_a), ptr(d_b), ptr(ws), ws.numel(),
-                                          stream_ptr(a.device)), "gnms_iou3d_backward")
-        return d_a, d_b, None, None, None, None
+        return _pair_backward(ctx, grad, "gnms_iou3d_backward", ctx.method) + (None,) * 4
 
 
 def iou3d_batched(a, b=None, method="generalized", from_params=False, want_bev=False, nms_overlap=False, out=None, nms_threshold=None):

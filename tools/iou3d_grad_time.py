@@ -1,8 +1,8 @@
-"""Times the cuboid gradient of the layer on the GPU, by the method of tools/iou_grad_time.py (whose measure / graphed it
-uses).  In one run, the variants alternating round by round:
+"""Times the cuboid gradient of the layer on the GPU, by the method of tools/iou_grad_time.py (whose measure / graphed /
+backward_of it uses).  In one run, the variants alternating round by round:
   per shape (B = 2, N = 500 and the headline shape B = 8, N = 4096), the BACKWARD behind one gnms_forward_with_iou3d (default mode), C ABI:
     plain   gnms_backward without a matrix gradient: the backward a caller had before (the same launches as ever)
-    sparse  gnms_backward_cuboids, default route: gnms_backward + bwd_masked_cuboids_kernel
+    sparse  gnms_backward_cuboids, default route: gnms_backward + bwd_masked_geometry_kernel<cuboids>
     dense   gnms_backward_cuboids, GNMS_BOXES_ROUTE_DENSE: gnms_backward with the matrix gradient + gnms_iou3d_backward (method 2)
   each eager (the ctypes call included) and replayed from a graph (the GPU's own time);
   gnms_iou3d_backward alone at B x N x N with a dense cotangent and with the masked layer's one-non-zero-per-row cotangent, beside
@@ -10,7 +10,6 @@ uses).  In one run, the variants alternating round by round:
 Device time by HIP events; per variant the median, minimum and the range of the rounds' medians (the run-to-run spread).
 usage: python tools/iou3d_grad_time.py [--iters K] [--rounds N] [--out FILE]  -> one JSON line per shape."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -22,32 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from groomed_nms_amd import _lib, synthetic  # noqa: E402
-from groomed_nms_amd import groomed_nms as GN  # noqa: E402
 from groomed_nms_amd._lib import check, ptr, stream_ptr  # noqa: E402
-from iou_grad_time import entry2, graphed, measure  # noqa: E402
-
-
-def backward_of(scores, params3d, variant):
-    """one gnms_forward_with_iou3d through the C ABI, then a closure that runs the backward alone on its workspace:
-    plain = gnms_backward (no matrix gradient), sparse / dense = gnms_backward_cuboids on that route"""
-    lib = _lib.load()
-    B, N = scores.shape
-    p = GN._params(0.4, "linear", 0.01, 0.3, False, True, True, 100, False, False)
-    prob, order, _, _, nv, ni = GN._outputs(B, N, scores.device, False)
-    overlap = torch.empty((B, N, N), device="cuda")
-    ws = torch.empty((max(lib.gnms_workspace_bytes(B, N, ctypes.byref(p)), 256),), dtype=torch.uint8, device="cuda")
-    check(lib.gnms_forward_with_iou3d(ptr(params3d), ptr(scores), B, N, N, None, ctypes.byref(p), ptr(overlap), ptr(prob), ptr(order), None, None,
-                                      ptr(nv), ptr(ni), ptr(ws), ws.numel(), stream_ptr()), "gnms_forward_with_iou3d")
-    gp = torch.linspace(-1, 2, N, device="cuda").repeat(B, 1).contiguous()
-    gs, gb = torch.empty_like(scores), torch.empty_like(params3d)
-    if variant == "plain":
-        return lambda: check(lib.gnms_backward(ptr(gp), ptr(scores), ptr(scores), B, N, N, None, ctypes.byref(p), ptr(gs), None, ptr(ws),
-                                               ws.numel(), stream_ptr()), "gnms_backward")
-    route = 1 if variant == "dense" else 0
-    nb = lib.gnms_backward_cuboids_scratch_bytes(B, N, N, ctypes.byref(p), 1, route)
-    scratch = torch.empty((max(nb, 256),), dtype=torch.uint8, device="cuda")
-    return lambda: check(lib.gnms_backward_cuboids(ptr(gp), ptr(params3d), ptr(scores), B, N, None, ctypes.byref(p), ptr(gs), ptr(gb), ptr(overlap),
-                                                   N, route, ptr(scratch), nb, ptr(ws), ws.numel(), stream_ptr()), "gnms_backward_cuboids")
+from iou_grad_time import backward_of, entry2, graphed, measure  # noqa: E402
 
 
 def entry3(B, N, cot):
@@ -71,7 +46,7 @@ def main():
     for B, N in ((2, 500), (8, 4096)):
         px, sc = synthetic.batch_3d(0, B, N, True, per=32)
         params, scores = torch.from_numpy(px).cuda(), torch.from_numpy(sc).cuda()
-        eager = {v: backward_of(scores, params, v) for v in ("plain", "sparse", "dense")}
+        eager = {v: backward_of(scores, params, v, "gnms_forward_with_iou3d", "gnms_backward_cuboids") for v in ("plain", "sparse", "dense")}
         res = dict(what="backward behind gnms_forward_with_iou3d, default mode", B=B, N=N, eager=measure(eager, a.iters, a.rounds))
         res["graph"] = measure({k: graphed(v) for k, v in eager.items()}, a.iters, a.rounds)
         lines.append(res)

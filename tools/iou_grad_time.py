@@ -1,7 +1,7 @@
 """Times the box gradient of the layer on the GPU.  In one run, the variants alternating round by round:
   per shape (B = 2, N = 500 and the headline shape B = 8, N = 4096), the BACKWARD behind one gnms_forward_with_iou2d (default mode), C ABI:
     plain   gnms_backward without a matrix gradient: the backward a caller had before (the same launches as ever)
-    sparse  gnms_backward_boxes, default route: gnms_backward + bwd_masked_boxes_kernel
+    sparse  gnms_backward_boxes, default route: gnms_backward + bwd_masked_geometry_kernel<boxes>
     dense   gnms_backward_boxes, GNMS_BOXES_ROUTE_DENSE: gnms_backward with the matrix gradient + gnms_iou2d_backward
   each eager (the ctypes call included) and replayed from a graph (the GPU's own time);
   gnms_iou2d_backward alone at B x N x N with a dense cotangent and with the masked layer's one-non-zero-per-row cotangent, beside
@@ -63,28 +63,29 @@ def graphed(fn):
     return g.replay
 
 
-def backward_of(scores, boxes, variant):
-    """one gnms_forward_with_iou2d through the C ABI, then a closure that runs the backward alone on its workspace:
-    plain = gnms_backward (no matrix gradient), sparse / dense = gnms_backward_boxes on that route"""
+def backward_of(scores, src, variant, forward="gnms_forward_with_iou2d", backward="gnms_backward_boxes"):
+    """one `forward` (gnms_forward_with_iou2d on boxes, gnms_forward_with_iou3d on cuboids: tools/iou3d_grad_time.py) through the C ABI, then
+    a closure that runs the backward alone on its workspace: plain = gnms_backward (no matrix gradient), sparse / dense = `backward`
+    (gnms_backward_boxes / gnms_backward_cuboids) on that route"""
     import ctypes
     lib = _lib.load()
     B, N = scores.shape
     p = GN._params(0.4, "linear", 0.01, 0.3, False, True, True, 100, False, False)
     prob, order, _, _, nv, ni = GN._outputs(B, N, scores.device, False)
-    iou = torch.empty((B, N, N), device="cuda")
+    matrix = torch.empty((B, N, N), device="cuda")
     ws = torch.empty((max(lib.gnms_workspace_bytes(B, N, ctypes.byref(p)), 256),), dtype=torch.uint8, device="cuda")
-    check(lib.gnms_forward_with_iou2d(ptr(boxes), ptr(scores), B, N, N, None, ctypes.byref(p), ptr(iou), ptr(prob), ptr(order), None, None,
-                                      ptr(nv), ptr(ni), ptr(ws), ws.numel(), stream_ptr()), "gnms_forward_with_iou2d")
+    check(getattr(lib, forward)(ptr(src), ptr(scores), B, N, N, None, ctypes.byref(p), ptr(matrix), ptr(prob), ptr(order), None, None,
+                                ptr(nv), ptr(ni), ptr(ws), ws.numel(), stream_ptr()), forward)
     gp = torch.linspace(-1, 2, N, device="cuda").repeat(B, 1).contiguous()
-    gs, gb = torch.empty_like(scores), torch.empty_like(boxes)
+    gs, gb = torch.empty_like(scores), torch.empty_like(src)
     if variant == "plain":
         return lambda: check(lib.gnms_backward(ptr(gp), ptr(scores), ptr(scores), B, N, N, None, ctypes.byref(p), ptr(gs), None, ptr(ws),
                                                ws.numel(), stream_ptr()), "gnms_backward")
     route = 1 if variant == "dense" else 0
-    nb = lib.gnms_backward_boxes_scratch_bytes(B, N, N, ctypes.byref(p), 1, route)
+    nb = getattr(lib, backward + "_scratch_bytes")(B, N, N, ctypes.byref(p), 1, route)
     scratch = torch.empty((max(nb, 256),), dtype=torch.uint8, device="cuda")
-    return lambda: check(lib.gnms_backward_boxes(ptr(gp), ptr(boxes), ptr(scores), B, N, None, ctypes.byref(p), ptr(gs), ptr(gb), ptr(iou), N,
-                                                 route, ptr(scratch), nb, ptr(ws), ws.numel(), stream_ptr()), "gnms_backward_boxes")
+    return lambda: check(getattr(lib, backward)(ptr(gp), ptr(src), ptr(scores), B, N, None, ctypes.byref(p), ptr(gs), ptr(gb), ptr(matrix), N,
+                                                route, ptr(scratch), nb, ptr(ws), ws.numel(), stream_ptr()), backward)
 
 
 def entry2(B, N, cot):
